@@ -29,7 +29,15 @@ rank 0, which un-permutes them on the device.
          frames. Rank 0 first renders the whole frame alone (the T1 leg, same steps) and the line
          reports efficiency = T1 / (N * T_N), both including what the N-rank run does per step.
 
-The JSON line carries `roofline` (fp32 VALU: oracle-counted fp32 ops per unit x units per launch /
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what the headline figure needs and nothing else: it
+sets up, warms up, times the K frames and prints the JSON line (`metric`, `value`, `unit`, `ms_per_step`, ...; the
+context and first set_scene times under `setup_ms`). `--dump-outputs DIR` also writes what the timed call left with
+its caller after the last frame, as float32 / float64 .npy files (dump_outputs below); the scene, camera and seeds are
+fixed, so two builds run with the same arguments can be compared output for output. Everything else the bench
+measures is behind `--full`: the further setup times, the frame-by-frame, primary-reuse, sustained-clock and 4D-view
+legs, the roofline and the CPU baseline (each leg also has its own --no-... switch).
+
+With `--full` the JSON line carries `roofline` (fp32 VALU: oracle-counted fp32 ops per unit x units per launch /
 average kernel time from HIP events on the launch stream, vs the 157.3 TFLOP/s gfx950 vector peak;
 `frac_executed` drops the Newton-loop ops the sampler table replaces), `setup_ms` (context + sampler
 table, scene upload + verification) and `cpu_baseline` (the scalar C++ oracle on this job's host
@@ -103,6 +111,12 @@ def parse_args(argv=None):
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample duration")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-ops", action="store_true", help="skip the oracle op count (profiling passes)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: the further setup times, the frame-by-frame, "
+                        "primary-reuse, sustained-clock and 4D-view legs (N = 1), the roofline and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed frames, write what the timed call computed (the frame after its last step, "
+                        "the intersection count) to DIR/<name>.npy")
     a = p.parse_args(argv)
     c = CONFIGS[a.config]
     for k in ("scene", "width", "height", "spp", "bounces", "format", "mode", "progressive"):
@@ -237,6 +251,26 @@ def pmc_profile(config, frames_per_dispatch):
     return None, None
 
 
+DUMP_SAMPLE_PIXELS = 3 << 20  # 48 MiB of float32 RGBA: a larger frame is dumped as a fixed sample of its pixels
+
+
+def dump_outputs(path, image, n_intersections):
+    """--dump-outputs: what the caller of the timed call holds after its last step, as DIR/<name>.npy.
+      frame.npy          float32: the frame buffer (rows, width, 4) in the frame format's values (f16 and rgba8
+                         widened exactly); a frame of more than DUMP_SAMPLE_PIXELS pixels is written as (n, 4), the
+                         pixels at a fixed seeded choice of flat indices y * width + x in ascending order
+      intersections.npy  float64 (1,): the device counter after the timed frames (every rank's summed)"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    img = image.numpy()
+    if img.shape[0] * img.shape[1] > DUMP_SAMPLE_PIXELS:
+        pick = np.random.default_rng(12345).choice(img.shape[0] * img.shape[1], DUMP_SAMPLE_PIXELS, replace=False)
+        img = img.reshape(-1, img.shape[-1])[np.sort(pick)]
+    np.save(os.path.join(path, "frame.npy"), img.astype(np.float32))
+    np.save(os.path.join(path, "intersections.npy"), np.array([n_intersections], dtype=np.float64))
+
+
 # ------------------------------------------------------------------------------------------ launcher
 def spawn_ranks(args):
     """`--gpus N` outside a launcher: N fresh processes via torch.distributed.run (this process has
@@ -363,17 +397,18 @@ def main():
     tracer.set_scene(scene)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
-    tracer.set_scene(scene)  # the same scene again: served from the verification cache
-    torch.cuda.synchronize()
-    t3 = time.perf_counter()
-    other = new_constants_scene(rt4, scene)  # a further new scene: radii and sun size not yet verified
-    tracer.set_scene(other)
-    torch.cuda.synchronize()
-    t4 = time.perf_counter()
-    tracer.set_scene(scene)
-    torch.cuda.synchronize()
-    setup = {"context_ms": (t1 - t0) * 1e3, "set_scene_ms": (t2 - t1) * 1e3, "set_scene_repeat_ms": (t3 - t2) * 1e3,
-             "set_scene_new_constants_ms": (t4 - t3) * 1e3}
+    setup = {"context_ms": (t1 - t0) * 1e3, "set_scene_ms": (t2 - t1) * 1e3}
+    if args.full:
+        tracer.set_scene(scene)  # the same scene again: served from the verification cache
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        other = new_constants_scene(rt4, scene)  # a further new scene: radii and sun size not yet verified
+        tracer.set_scene(other)
+        torch.cuda.synchronize()
+        t4 = time.perf_counter()
+        tracer.set_scene(scene)
+        torch.cuda.synchronize()
+        setup.update({"set_scene_repeat_ms": (t3 - t2) * 1e3, "set_scene_new_constants_ms": (t4 - t3) * 1e3})
 
     base = rt4.make_uniforms(plan.width, plan.height, samples=args.spp, reflections=args.bounces, seed=args.seed)
     frame_no = [0]
@@ -426,6 +461,7 @@ def main():
     reg = rt4.region(**plan.region_args(rank))
     frame = torch.zeros((plan.rows_max, plan.width, 4), dtype=tdt, device=dev)  # padded shard (gather)
     gathers = []
+    assembled = [None]  # N > 1, rank 0: the frame the last gather assembled
 
     def render():
         tracer.render_device_ex(uniforms(), reg, frame.data_ptr(), fmt, plan.width, counter.data_ptr(), sptr)
@@ -438,9 +474,9 @@ def main():
         # fails (gloo) or when sync() finds the report (RCCL): status 1 naming the rank, no hang (shard.py)
         try:
             if rehearse:
-                shard.gather_frame(frame.cpu(), plan, rank)
+                assembled[0] = shard.gather_frame(frame.cpu(), plan, rank)
             else:
-                shard.gather_frame(frame, plan, rank)  # the frame assembled (un-permuted) on rank 0
+                assembled[0] = shard.gather_frame(frame, plan, rank)  # the frame assembled (un-permuted) on rank 0
         except Exception as e:  # noqa: BLE001 - any failure of the collective ends every rank
             shard.exit_failed(rank, f"{type(e).__name__}: {e}")
 
@@ -510,12 +546,15 @@ def main():
 
     n_local = int(counter.item())
     evaluated = tracer.evaluated() if args.primary_reuse else None
+    dump_image = None
+    if args.dump_outputs and rank == 0:  # a host copy now: the legs below render into the same frame buffer
+        dump_image = (frame if world == 1 else assembled[0]).cpu()
 
     # Extra leg (N = 1, pipelined headline): the same frames, one launch per frame (rt4_render_device_ex),
     # as the reference draws one frame per loop iteration (main.cpp:93, windows.cpp:45): the per-launch
     # drain is paid every frame. Reported beside the headline, never as value.
     fbf_leg = None
-    if world == 1 and pipelined and not args.no_fbf_leg:
+    if args.full and world == 1 and pipelined and not args.no_fbf_leg:
         frame_no[0] = 0
         frame.zero_()
         for _ in range(args.warmup):
@@ -548,7 +587,7 @@ def main():
     # Extra leg (N = 1): the same frames with RT4_FLAG_PRIMARY_REUSE, reported beside the headline
     # (a reference-equivalent rate, with the evaluated count next to it).
     reuse_leg = None
-    if world == 1 and not args.primary_reuse and not args.no_reuse_leg:
+    if args.full and world == 1 and not args.primary_reuse and not args.no_reuse_leg:
         t_r = rt4.Tracer(device=gpu, flags=flags | rt4.FLAG_PRIMARY_REUSE, scene=scene)
         frame_no[0] = 0
         frame.zero_()
@@ -594,7 +633,7 @@ def main():
     # past the ramp already. Two launches' worth of frames (at least the timed frames, so no launch drains more often
     # than the headline's), fewer when 150 ms of load takes fewer.
     steady_leg = None
-    if world == 1 and pipelined and not args.no_steady_leg and kernel_ms * args.steps < 150.0:
+    if args.full and world == 1 and pipelined and not args.no_steady_leg and kernel_ms * args.steps < 150.0:
         fpl_s = tracer.frames_per_launch(reg.w, reg.h)
         n_st = max(args.steps, min(2 * fpl_s, int(150.0 / max(kernel_ms, 1e-3))))
         frame_no[0] = 0
@@ -617,7 +656,7 @@ def main():
             "kernel_ms": ms_s, "intersections_per_step": n_s / n_st,
         }
     sections_leg = None
-    if world == 1 and not args.no_sections_leg:
+    if args.full and world == 1 and not args.no_sections_leg:
         sections_leg = sections_loop_leg(rt4, torch, gpu, flags, scene, stream, tracer)
     if world > 1:
         st = torch.tensor([elapsed, kernel_ms, gather_ms], dtype=torch.float64, device=comm_dev)
@@ -695,7 +734,7 @@ def main():
         if strong:
             line["t1_ms"] = t1_ms if world > 1 else ms_per_step
             line["efficiency"] = (line["t1_ms"] / (world * ms_per_step)) if line["t1_ms"] else None
-        if not args.no_ops:
+        if args.full and not args.no_ops:
             opu, opu_exec, _ = ops_per_unit(rt4, scene, base, plan.width, plan.height, cpus["threads"])
             achieved = opu * units_per_launch / (kernel_ms * 1e-3) / 1e12
             achieved_exec = (opu if args.no_lut else opu_exec) * units_per_launch / (kernel_ms * 1e-3) / 1e12
@@ -779,8 +818,10 @@ def main():
                     line["roofline"]["gather_ceiling_per_s"] = ceiling
             if prof and der.get("ea_read_latency_cycles"):
                 line["roofline"]["ea_read_latency_cycles"] = der["ea_read_latency_cycles"]
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(rt4, scene, base, plan.width, plan.rows_max, args.cpu_seconds, cpus)
+        if dump_image is not None:
+            dump_outputs(args.dump_outputs, dump_image, n_total)
         print(json.dumps(line), flush=True)
     tracer.close()
     if world > 1:

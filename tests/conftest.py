@@ -8,8 +8,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-REFERENCE = "/root/reference"  # present only in the build container, never on the GPU box
-
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (run on the GPU box via gpurun)")
@@ -48,7 +46,3 @@ def tracer_lut(rt4):
     t = rt4.Tracer(device=0, flags=rt4.FLAG_SAMPLER_LUT)
     yield t
     t.close()
-
-
-def reference_available():
-    return os.path.isdir(os.path.join(REFERENCE, "scenes"))

@@ -34,6 +34,36 @@ def test_default_is_config2_and_overrides_win():
     assert a.mode == "weak" and a.gather == "final"
 
 
+def test_a_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files; a frame above the size limit is a seeded sample of its pixels,
+    the same pixels in every run."""
+    import numpy as np
+    import torch
+
+    assert bench.DUMP_SAMPLE_PIXELS * 16 + 8 <= 64 << 20  # the largest dump: RGBA float32 pixels and the count
+    img = torch.arange(6 * 5 * 4, dtype=torch.float32).reshape(6, 5, 4).to(torch.float16)
+    bench.dump_outputs(str(tmp_path / "a"), img, 12345678901)
+    frame = np.load(tmp_path / "a" / "frame.npy")
+    assert frame.dtype == np.float32 and np.array_equal(frame, img.numpy().astype(np.float32))
+    count = np.load(tmp_path / "a" / "intersections.npy")
+    assert count.dtype == np.float64 and count.tolist() == [12345678901.0]
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_PIXELS", 7)
+    bench.dump_outputs(str(tmp_path / "b"), img, 1)
+    bench.dump_outputs(str(tmp_path / "c"), img, 1)
+    sample = np.load(tmp_path / "b" / "frame.npy")
+    assert sample.dtype == np.float32 and sample.shape == (7, 4)
+    assert np.array_equal(sample, np.load(tmp_path / "c" / "frame.npy"))
+    px = sample[:, 0] / 4  # channel 0 of pixel i holds 4 * i: distinct pixels of the frame in ascending order
+    assert np.all(np.diff(px) > 0) and np.all(px == np.round(px)) and px[-1] < 30
+
+
 def test_host_cpus_respects_the_share(monkeypatch):
     monkeypatch.setenv("OMP_NUM_THREADS", "3")
     c = bench.host_cpus()

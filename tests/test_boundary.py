@@ -8,8 +8,6 @@ import re
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, reference_available
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rt4.h")
 GOLDEN32 = np.float32(1.61803399)
@@ -144,21 +142,6 @@ def test_psi_constraint(rt4):
 
 
 # ------------------------------------------------------------------------------ scenes
-REF_SCENES = {"Шар": "sphere", "Комната": "room", "Фигура": "tiger", "Четырёхмерный": "cylinder4d",
-              "Гиперкуб": "hypercube"}
-
-
-@pytest.mark.skipif(not reference_available(), reason="reference tree not mounted (GPU box)")
-def test_reference_scene_files_parse_to_builtins(rt4):
-    files = sorted(glob.glob(os.path.join(REFERENCE, "scenes", "*.frag")))
-    assert len(files) == 5
-    for f in files:
-        name = [v for k, v in REF_SCENES.items() if k in os.path.basename(f)][0]
-        assert rt4.Scene.load_frag(f).to_bytes() == rt4.Scene.builtin(name).to_bytes(), name
-    full = rt4.Scene.load_frag(os.path.join(REFERENCE, "executable", "shader.frag"))
-    assert full.to_bytes() == rt4.Scene.builtin("tiger").to_bytes()  # shipped default scene
-
-
 def test_builtin_scene_values(rt4):
     s = rt4.Scene.builtin("room").desc
     assert s.n_spaces == 8 and s.n_spheres == 2 and s.final_light_mode == rt4.FINAL_LIGHT_CONSTANT

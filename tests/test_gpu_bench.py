@@ -20,7 +20,7 @@ def run_bench(*args, timeout=110):
 
 
 def test_bench_json_line():
-    d = run_bench("--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    d = run_bench("--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "setup_ms", "value_per_gpu"):
         assert k in d, k
@@ -48,6 +48,37 @@ def test_bench_json_line():
     assert st["intersections_per_step"] == d["intersections_per_step"] and st["frames"] >= 2 and st["value"] > 1e9
     if rf.get("frac_counters"):
         assert st["frac_counters"] > rf["frac_counters"] * 0.9  # the same work over a time at least as short
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(rt4, oracle, tmp_path):
+    """A plain run measures the headline only (no leg, roofline or CPU baseline: those are behind --full), and
+    --dump-outputs writes the frame and the count the timed call left, here checked against the oracle bit for bit."""
+    import numpy as np
+
+    w, h, steps, warmup = 96, 60, 2, 1
+    d = run_bench("--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--width", str(w), "--height", str(h),
+                  "--spp", "2", "--bounces", "3", "--dump-outputs", str(tmp_path / "out"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and d["dtype"] == "fp32"
+    assert d["value"] == pytest.approx(d["intersections_per_step"] / (d["ms_per_step"] * 1e-3))
+    for k in ("roofline", "cpu_baseline", "frame_by_frame_leg", "primary_reuse_leg", "steady_clock_leg",
+              "sections_loop_leg"):
+        assert k not in d, k
+    assert set(d["setup_ms"]) == {"context_ms", "set_scene_ms"}
+    assert sorted(os.listdir(tmp_path / "out")) == ["frame.npy", "intersections.npy"]
+    frame = np.load(tmp_path / "out" / "frame.npy")
+    count = np.load(tmp_path / "out" / "intersections.npy")
+    assert frame.dtype == np.float32 and frame.shape == (h, w, 4)
+    assert count.dtype == np.float64 and count.shape == (1,)
+    scene = rt4.Scene.named("sphere")
+    u = rt4.make_uniforms(w, h, samples=2, reflections=3, seed=12345)
+    cpu, timed = np.zeros((h, w, 4), np.float32), 0
+    for n in range(warmup + steps):  # the warmup frames and the timed ones accumulate in one frame buffer
+        _, k = oracle.render_fmt(scene.desc, u, rt4.region(w, h), rt4.FRAME_RGBA32F, frame=cpu, threads=4)
+        timed += k if n >= warmup else 0
+    assert count[0] == timed == d["intersections_per_step"] * steps
+    assert np.array_equal(frame.view(np.uint32), cpu.view(np.uint32))
 
 
 def test_bench_strong_config4_one_gpu():

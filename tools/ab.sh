@@ -106,7 +106,7 @@ check)
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 \
     || { echo "smoke failed"; tail -20 "$OUT/smoke.log"; exit 1; }
   tail -2 "$OUT/smoke.log"
-  timeout -k 10 300 python3 "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.log" 2>&1 \
+  timeout -k 10 300 python3 "$ROOT/bench.py" --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.log" 2>&1 \
     || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 1; }
   tail -1 "$OUT/bench.log" | cut -c1-400
   ;;
