@@ -67,8 +67,7 @@ struct alignas(32) SphereCull {
 // The same cull for the 2-axis cylinders (rt4_fast.h cyl_cand_cull): their exact test is sphere_cand on the ray
 // projected onto the cylinder's 2-plane (shader.frag:251-267), and the derivation above is in terms of d2 and
 // dot_pord alone, whatever the ray's direction, so it holds for the projected ray as it is. Only d2_out and r2m
-// are used (the centre is the cylinder's point). A tiger's axes pair skips its shared sphere core when both of its
-// radii cull; one quarter of the in-wave split when its own radius does.
+// are used (the centre is the cylinder's point).
 // Pre-normalisation form (rt4_fast.h cyl_cand_precull): cyl_project normalises the projected direction e (two
 // lengths, four divisions) before the test needs dp = dot(po, RN(e / len)). With u = 2^-24, |dp - s| <= 8.1u sqrt(d2)
 // for s = dot(po, e) / |e| (the division and sqrt round once each, the two dots by gamma_4), so
@@ -144,7 +143,7 @@ struct SceneAux {
   SphereCull sphere_cull[RT4_MAX_SPHERES];
   BoundBall union_bound[RT4_MAX_UNIONS];
   BoundBall tiger_bound[RT4_MAX_TIGERS];
-  // Hypercube (rt4_fast.h cube_cand): a face hit needs |q - c|^2 <= |cpt - c|^2 + 3 r^2 for the face
+  // Hypercube (rt4_fast.h hypercube_cand): a face hit needs |q - c|^2 <= |cpt - c|^2 + 3 r^2 for the face
   // square (orthonormal normal + axes); only center and r2m are used. A face that is not nearly
   // parallel to the ray (cos_dn^2 >= 1e-12 |d|^2) has a finite hit point, so for a ray whose line
   // clears the ball its extent test fails: skipped. Nearly parallel faces (the +inf / NaN "hits" of
@@ -158,7 +157,6 @@ struct SceneAux {
   // their schedules stay as they were)
   SphereCull cyl_cull[RT4_MAX_CYLINDERS];
   SphereCull union_cull[RT4_MAX_UNIONS][2];
-  SphereCull tiger_cull[RT4_MAX_TIGERS][4];  // inner_cyl1, outer_cyl1, inner_cyl2, outer_cyl2 (as tiger_r)
 };
 
 static_assert(offsetof(SceneAux, prims) - offsetof(SceneAux, hyper_cells) == sizeof(float) * 8 * 24,

@@ -14,17 +14,6 @@
 #ifndef RT4_SPHERE_CULL
 #define RT4_SPHERE_CULL 1
 #endif
-#ifndef RT4_HYPER_AXIS_TIGER
-#define RT4_HYPER_AXIS_TIGER 1  // the axis form in the tiger kernels too: r05-v48, config 5 +4.3 % (r05_ab.txt); it
-                                // measured 4.5 % slower before r05-v45's register savings
-#endif
-#ifndef RT4_HYPER_AXIS
-#define RT4_HYPER_AXIS 1  // hypercube cull: one-component form for axis-aligned canonical cells (rt4_aux.h
-                          // hyper_axis)
-#endif
-#ifndef RT4_HYPER_PENDING
-#define RT4_HYPER_PENDING 1  // hypercube: per-lane pending-cell loop (hypercube_cand) instead of 8 cells in order
-#endif
 constexpr int HYPER_CELLS_LDS = 8 * 6;  // float4s of hypercube 0's cells staged ahead of the primitive table
 #ifndef RT4_BOUND_SKIP
 #define RT4_BOUND_SKIP 1  // bounding-ball skips for tiger / union / hypercube faces (rt4_aux.h BoundBall)
@@ -171,23 +160,16 @@ __device__ __forceinline__ void sphere_dist2(const SphereCore2& c, float r, floa
   }
 }
 
-#ifndef RT4_SPACE_SIGN_DOT
-#define RT4_SPACE_SIGN_DOT 1  // space_cand: cos_dh = sgn * dot(norm, drct) (r06-v53, with RT4_BALL_BEHIND)
-#endif
 __device__ __forceinline__ Cand space_cand(const rt4_scene_desc* __restrict__ S, int i, const Ray& ray) {  // :231-239
   const rt4_space& s = S->spaces[i];
   const V4 sn = ld4(s.norm);
   const float dot_vn = dot(sub(ld4(s.point), ray.point), sn);
   const float sgn = dot_vn > 0.0f ? 1.0f : (dot_vn < 0.0f ? -1.0f : 0.0f);
-#if RT4_SPACE_SIGN_DOT
-  // dot(sn * sgn, d) as sgn * dot(sn, d) (round 6, A/B knob): for sgn = +-1 the fma chain of the negated vector is the
+  // the shader's dot(sn * sgn, d) as sgn * dot(sn, d) (r06-v53): for sgn = +-1 the fma chain of the negated vector is the
   // exact negation of the plain one (round-to-nearest-even is symmetric), except that an exact zero keeps +0 where the
   // negation gives -0; for sgn = 0 both are a zero (or the same NaN class from non-finite operands). A zero is below
   // SMALL_F either way, and a nonzero cos_dh is bit-identical, so the candidate is too: 3 VALU fewer per space.
   const float cos_dh = sgn * dot(sn, ray.drct);
-#else
-  const float cos_dh = dot(mul(sn, sgn), ray.drct);
-#endif
   Cand c{true, sgn < 0.0f, 0.0f, 0.0f, static_cast<uint32_t>(i)};
   if (cos_dh < SMALL_F) return no_cand();
   c.dist = rdiv(__builtin_fabsf(dot_vn), cos_dh);
@@ -251,10 +233,6 @@ __device__ __forceinline__ Cand cyl_cand_precull(V4 cp, V4 a1, V4 a2, const Ray&
                         // normalisation, 2 also before it (config 5 -0.4 %: few waves cull every lane, and the
                         // extra test costs more than the divisions it skips; profiles/r05_ab.txt)
 #endif
-#ifndef RT4_TIGER_CULL
-#define RT4_TIGER_CULL 0  // the sphere cull for the tiger's axes pairs and split quarters: config 4 -1.3 %, config 5
-                          // +-0 (r05_ab.txt), off
-#endif
 
 // dist_to_axes_plane(..)^2 without the sqrt (shader.frag:270-275)
 __device__ __forceinline__ float axes_dist_sq(float dist, const Ray& ray, V4 cp, V4 a1, V4 a2) {
@@ -296,17 +274,9 @@ __device__ __forceinline__ Cand union_cand(const rt4_scene_desc* __restrict__ S,
 // outer = true/false, kept iff the other pair's axes distance d satisfies lt <= d^2 <= gt.
 __device__ __forceinline__ Cand tiger_pair(V4 cp, V4 a1, V4 a2, float r_in, float r_out, const DivC& dc_in,
                                            const DivC& dc_out, V4 op, V4 oa1, V4 oa2, float gt, float lt,
-                                           const Ray& ray, uint32_t id_base, const SphereCull& k_in,
-                                           const SphereCull& k_out) {
+                                           const Ray& ray, uint32_t id_base) {
   const CylProj p = cyl_project(cp, a1, a2, ray);
   if (p.miss) return no_cand();
-#if RT4_TIGER_CULL
-  {  // both radii miss (rt4_aux.h SphereCull): no face of this pair can hit
-    const V4 po = sub(cp, p.r12.point);
-    const float d2 = dot(po, po), dp = dot(po, p.r12.drct);
-    if (sphere_culled(d2, dp, k_in.d2_out, k_in.r2m) && sphere_culled(d2, dp, k_out.d2_out, k_out.r2m)) return no_cand();
-  }
-#endif
   SphereCore2 c_in, c_out;
   sphere_core_pair(cp, r_in, dc_in, r_out, dc_out, p.r12, c_in, c_out);
   Cand res = no_cand();
@@ -349,10 +319,9 @@ __device__ __forceinline__ Cand tiger_cand(const rt4_scene_desc* __restrict__ S,
   const V4 pA = ld4(t.inner_cyl1.point), a1 = ld4(t.inner_cyl1.axis1), a2 = ld4(t.inner_cyl1.axis2);
   const V4 pB = ld4(t.inner_cyl2.point), a3 = ld4(t.inner_cyl2.axis1), a4 = ld4(t.inner_cyl2.axis2);
   const Cand lo = tiger_pair(pA, a1, a2, t.inner_cyl1.r, t.outer_cyl1.r, X->tiger_r[i][0], X->tiger_r[i][1], pB, a3,
-                             a4, X->tiger_gt[i][0], X->tiger_lt[i][0], ray, base, X->tiger_cull[i][0], X->tiger_cull[i][1]);
+                             a4, X->tiger_gt[i][0], X->tiger_lt[i][0], ray, base);
   const Cand hi = tiger_pair(pB, a3, a4, t.inner_cyl2.r, t.outer_cyl2.r, X->tiger_r[i][2], X->tiger_r[i][3], pA, a1,
-                             a2, X->tiger_gt[i][1], X->tiger_lt[i][1], ray, base + 2, X->tiger_cull[i][2],
-                             X->tiger_cull[i][3]);
+                             a2, X->tiger_gt[i][1], X->tiger_lt[i][1], ray, base + 2);
   return closest(lo, hi);
 }
 
@@ -384,18 +353,6 @@ __device__ __forceinline__ Cand tiger_quarter(const rt4_scene_desc* __restrict__
   const uint32_t id = base + (pb ? 2u : 0u) + (outer ? 1u : 0u);
   const CylProj p = cyl_project(cp, ax1, ax2, ray);
   if (p.miss) return no_cand();
-#if RT4_TIGER_CULL
-  {  // this radius misses (rt4_aux.h SphereCull)
-    const SphereCull& k0 = X->tiger_cull[i][0];
-    const SphereCull& k1 = X->tiger_cull[i][1];
-    const SphereCull& k2 = X->tiger_cull[i][2];
-    const SphereCull& k3 = X->tiger_cull[i][3];
-    const float kd = pb ? (outer ? k3.d2_out : k2.d2_out) : (outer ? k1.d2_out : k0.d2_out);
-    const float kr = pb ? (outer ? k3.r2m : k2.r2m) : (outer ? k1.r2m : k0.r2m);
-    const V4 po = sub(cp, p.r12.point);
-    if (sphere_culled(dot(po, po), dot(po, p.r12.drct), kd, kr)) return no_cand();
-  }
-#endif
   SphereCore2 c, c_same;
   sphere_core_pair(cp, r, dc, r, dc, p.r12, c, c_same);  // both cores of one radius: the pair's shared part + it
   if (c.miss) return no_cand();
@@ -411,26 +368,8 @@ __device__ __forceinline__ Cand tiger_quarter(const rt4_scene_desc* __restrict__
   return closest(c_o, c_i);
 }
 
-// far: the ray's line clears the hypercube's ball (rt4_aux.h hyper_bound); l2 = |drct|^2
-__device__ __forceinline__ Cand cube_cand(const rt4_cube& c, const Ray& ray, uint32_t id, bool far, float l2) {  // :352-366
-  const V4 cpt = ld4(c.point), cn = ld4(c.norm);
-  const V4 vec_n = neg(cn);
-  const float h = dot(sub(cpt, ray.point), vec_n);
-  const float cos_dn = dot(ray.drct, vec_n);
-  if (h < 0.0f || cos_dn < 0.0f) return no_cand();
-  if (far && cos_dn * cos_dn >= 1e-12f * l2) return no_cand();  // finite hit point, outside the ball
-  const float dist = rdiv(h, cos_dn);
-  const V4 vec_cp = sub(mad(ray.drct, dist, ray.point), cpt);
-  if (__builtin_fabsf(dot(vec_cp, ld4(c.x))) > c.r || __builtin_fabsf(dot(vec_cp, ld4(c.y))) > c.r ||
-      __builtin_fabsf(dot(vec_cp, ld4(c.z))) > c.r)
-    return no_cand();
-  return Cand{true, false, dist, 0.0f, id};
-}
-
-__device__ __forceinline__ Cand hypercube_cand_seq(const rt4_scene_desc* __restrict__ S, const SceneAux* __restrict__ X,
-                                                   int i, uint32_t base, const Ray& ray);
-
-// cube_cand's exact test from a cell staged in LDS (rt4_aux.h hyper_cells): the same floats, the same ops
+// cube_intersection's exact test (shader.frag:352-366) from a cell staged in LDS (rt4_aux.h hyper_cells): the
+// same floats, the same ops
 __device__ __forceinline__ bool cell_hit(const float4* cell, const Ray& ray, float& dist) {
   const float4 p4 = cell[0], n4 = cell[1], x4 = cell[2], y4 = cell[3], z4 = cell[4];
   const float r = cell[5].x;
@@ -449,99 +388,71 @@ __device__ __forceinline__ bool cell_hit(const float4* cell, const Ray& ray, flo
 // (h < 0 || cos_dn < 0, the far-face skip) for all lanes, then each lane's remaining candidate cells
 // in cell order until the first hit, read from LDS. Same first-hit-in-order result; a wave pays for
 // max-over-lanes(candidates tried) exact tests instead of all 8 cells.
-template <bool PENDING, bool AXIS>
 __device__ __forceinline__ Cand hypercube_cand(const rt4_scene_desc* __restrict__ S, const SceneAux* __restrict__ X,
                                                const float4* cells, int i, uint32_t base, const Ray& ray) {
-  if constexpr (PENDING) {
-    const rt4_hypercube& hc = S->hypercubes[i];
-    float l2 = 0.0f;
-    bool far = false;
-#if RT4_BOUND_SKIP
-    {
-      const f16v k = *reinterpret_cast<const f16v*>(&X->hyper_bound[i]);
-      const V4 pc = sub(V4{k[0], k[1], k[2], k[3]}, ray.point);
-      const float a = dot(pc, pc), b = dot(pc, ray.drct);
-      l2 = dot(ray.drct, ray.drct);
-      far = a < 1e30f && l2 > 1e-30f && l2 < 1e30f && (a - fmaf_(4e-6f, a, k[12])) * l2 > b * b;
-    }
-#endif
-    // Axis-aligned canonical cells (rt4_aux.h hyper_axis) and a finite ray in every lane: vec_n is
-    // -+e_(k&3), so h = dot(cpt - p, vec_n) and cos_dn = dot(d, vec_n) are exactly -+(one component)
-    // (the other products are +-0, which leave a nonzero sum unchanged); only the sign of a zero
-    // result can differ, and the tests below do not see it (cos_dn enters squared).
-    bool axis = false;
-    if constexpr (AXIS)
-      axis = X->hyper_axis[i] != 0 &&
-             !__any(!(__builtin_fabsf(ray.point.x) < 1e30f && __builtin_fabsf(ray.point.y) < 1e30f &&
-                      __builtin_fabsf(ray.point.z) < 1e30f && __builtin_fabsf(ray.point.w) < 1e30f &&
-                      __builtin_fabsf(ray.drct.x) < 1e30f && __builtin_fabsf(ray.drct.y) < 1e30f &&
-                      __builtin_fabsf(ray.drct.z) < 1e30f && __builtin_fabsf(ray.drct.w) < 1e30f));
-    uint32_t cand = 0;
-    if (axis) {
-      const float pc[4] = {ray.point.x, ray.point.y, ray.point.z, ray.point.w};
-      const float dc[4] = {ray.drct.x, ray.drct.y, ray.drct.z, ray.drct.w};
-#pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const float d = hc.cubes[k].point[k & 3] - pc[k & 3];
-        const float h = k < 4 ? -d : d;
-        const float cos_dn = k < 4 ? -dc[k & 3] : dc[k & 3];
-        const bool rejected = h < 0.0f || cos_dn < 0.0f || (far && cos_dn * cos_dn >= 1e-12f * l2);
-        cand |= rejected ? 0u : (1u << k);
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const rt4_cube& c = hc.cubes[k];
-        const V4 vec_n = neg(ld4(c.norm));
-        const float h = dot(sub(ld4(c.point), ray.point), vec_n);
-        const float cos_dn = dot(ray.drct, vec_n);
-        const bool rejected = h < 0.0f || cos_dn < 0.0f || (far && cos_dn * cos_dn >= 1e-12f * l2);
-        cand |= rejected ? 0u : (1u << k);
-      }
-    }
-    Cand res = no_cand();
-    while (cand) {
-#ifdef RT4_LANESTATS  // diagnostic: pending-cell trips and their active lanes (counter[58], [59])
-      {
-        const unsigned long long ex = __builtin_amdgcn_read_exec();
-        if (rt4_ls_counter && (threadIdx.x & 63u) == static_cast<unsigned>(__builtin_ctzll(ex))) {
-          atomicAdd(rt4_ls_counter + 58, 1ull);
-          atomicAdd(rt4_ls_counter + 59, static_cast<unsigned long long>(__popcll(ex)));
-        }
-      }
-#endif
-      const int k = __builtin_ctz(cand);
-      cand &= cand - 1u;
-      float dist;
-      if (cell_hit(cells + 6 * k, ray, dist)) {
-        res = Cand{true, false, dist, 0.0f, base + static_cast<uint32_t>(k)};
-        cand = 0u;
-      }
-    }
-    return res;
-  } else {
-    return hypercube_cand_seq(S, X, i, base, ray);
-  }
-}
-
-__device__ __forceinline__ Cand hypercube_cand_seq(const rt4_scene_desc* __restrict__ S, const SceneAux* __restrict__ X,
-                                                   int i, uint32_t base, const Ray& ray) {  // :394-400
   const rt4_hypercube& hc = S->hypercubes[i];
   float l2 = 0.0f;
   bool far = false;
 #if RT4_BOUND_SKIP
   {
-    const f16v k = *reinterpret_cast<const f16v*>(&X->hyper_bound[i]);  // centre 0-3, r2m 12
+    const f16v k = *reinterpret_cast<const f16v*>(&X->hyper_bound[i]);
     const V4 pc = sub(V4{k[0], k[1], k[2], k[3]}, ray.point);
     const float a = dot(pc, pc), b = dot(pc, ray.drct);
     l2 = dot(ray.drct, ray.drct);
     far = a < 1e30f && l2 > 1e-30f && l2 < 1e30f && (a - fmaf_(4e-6f, a, k[12])) * l2 > b * b;
   }
 #endif
-  Cand res = no_cand();
+  // Axis-aligned canonical cells (rt4_aux.h hyper_axis) and a finite ray in every lane: vec_n is
+  // -+e_(k&3), so h = dot(cpt - p, vec_n) and cos_dn = dot(d, vec_n) are exactly -+(one component)
+  // (the other products are +-0, which leave a nonzero sum unchanged); only the sign of a zero
+  // result can differ, and the tests below do not see it (cos_dn enters squared).
+  // (in the tiger kernels too since r05-v48: config 5 +4.3 %, profiles/r05_ab.txt)
+  const bool axis = X->hyper_axis[i] != 0 &&
+                    !__any(!(__builtin_fabsf(ray.point.x) < 1e30f && __builtin_fabsf(ray.point.y) < 1e30f &&
+                             __builtin_fabsf(ray.point.z) < 1e30f && __builtin_fabsf(ray.point.w) < 1e30f &&
+                             __builtin_fabsf(ray.drct.x) < 1e30f && __builtin_fabsf(ray.drct.y) < 1e30f &&
+                             __builtin_fabsf(ray.drct.z) < 1e30f && __builtin_fabsf(ray.drct.w) < 1e30f));
+  uint32_t cand = 0;
+  if (axis) {
+    const float pc[4] = {ray.point.x, ray.point.y, ray.point.z, ray.point.w};
+    const float dc[4] = {ray.drct.x, ray.drct.y, ray.drct.z, ray.drct.w};
 #pragma unroll
-  for (int k = 0; k < 8; k++) {
-    if (!res.hit) res = cube_cand(hc.cubes[k], ray, base + k, far, l2);
+    for (int k = 0; k < 8; k++) {
+      const float d = hc.cubes[k].point[k & 3] - pc[k & 3];
+      const float h = k < 4 ? -d : d;
+      const float cos_dn = k < 4 ? -dc[k & 3] : dc[k & 3];
+      const bool rejected = h < 0.0f || cos_dn < 0.0f || (far && cos_dn * cos_dn >= 1e-12f * l2);
+      cand |= rejected ? 0u : (1u << k);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const rt4_cube& c = hc.cubes[k];
+      const V4 vec_n = neg(ld4(c.norm));
+      const float h = dot(sub(ld4(c.point), ray.point), vec_n);
+      const float cos_dn = dot(ray.drct, vec_n);
+      const bool rejected = h < 0.0f || cos_dn < 0.0f || (far && cos_dn * cos_dn >= 1e-12f * l2);
+      cand |= rejected ? 0u : (1u << k);
+    }
+  }
+  Cand res = no_cand();
+  while (cand) {
+#ifdef RT4_LANESTATS  // diagnostic: pending-cell trips and their active lanes (counter[58], [59])
+    {
+      const unsigned long long ex = __builtin_amdgcn_read_exec();
+      if (rt4_ls_counter && (threadIdx.x & 63u) == static_cast<unsigned>(__builtin_ctzll(ex))) {
+        atomicAdd(rt4_ls_counter + 58, 1ull);
+        atomicAdd(rt4_ls_counter + 59, static_cast<unsigned long long>(__popcll(ex)));
+      }
+    }
+#endif
+    const int k = __builtin_ctz(cand);
+    cand &= cand - 1u;
+    float dist;
+    if (cell_hit(cells + 6 * k, ray, dist)) {
+      res = Cand{true, false, dist, 0.0f, base + static_cast<uint32_t>(k)};
+      cand = 0u;
+    }
   }
   return res;
 }
@@ -573,26 +484,14 @@ __device__ __forceinline__ void for_count(int runtime_n, F&& body) {
 
 // True when the ray's line stays clear of a bounding ball (rt4_aux.h BoundBall): the group's exact test
 // would report no hit. One 32-B scalar load, three dots.
-// RT4_BALL_BEHIND (round 6): also when the ball is behind the ray: the origin outside the inflated ball (a > R2m) and
+// Also when the ball is behind the ray (round 6): the origin outside the inflated ball (a > R2m) and
 // the centre not ahead (b <= 0). Every forward point p + t d (t >= 0) is then at squared distance a - 2 t b + t^2 l2
 // >= a > R2m from the centre, and the exact tests report only forward hits (dist = sqrt(..) >= 0, t = s / |e| in the
 // projected plane) inside the ball (the derivation in rt4_aux.h, which R2m's 1e-3 inflation covers); the NaN-distance
 // hits of origins near a cylinder keep the exact path through the same band check. So the skip is exact too.
-#ifndef RT4_BALL_BEHIND_MAX
-#define RT4_BALL_BEHIND_MAX 1  // r06-v54: the behind test as max(b, 0) inside the line test (fits the mirror room's registers)
-#endif
-#ifndef RT4_BALL_BEHIND
-#define RT4_BALL_BEHIND 2  // r06-v53: 1 (not the closed rooms; config 5 +1.5 %); r06-v54: 2, every kernel (config 4 +3.1 %)
-#endif
-// BEHIND: the kernel's shape takes the second test (RT4_BALL_BEHIND; not in the closed rooms' kernels, >= 3 spaces,
-// where it spilled in the loop at their wave bound)
-template <uint32_t SH>
-constexpr bool ball_behind_of() {
-  return RT4_BALL_BEHIND != 0 && (RT4_BALL_BEHIND == 2 || ((SH >> 8) & 0xFFu) < 4);
-}
-// LINE = false: only the occlusion test (the hypercube's ball: its parallel faces' +inf hits forbid the line skip)
-template <bool BEHIND = false, bool OCC = false, bool LINE = true>
-__device__ __forceinline__ bool far_from(const BoundBall& bb, const Ray& ray, const Cand* acc = nullptr) {
+// (r06-v53: config 5 +1.5 %; r06-v54, in every kernel with the behind test as max(b, 0) inside the line test, which
+// fits the mirror room's registers: config 4 +3.1 %)
+__device__ __forceinline__ bool far_from(const BoundBall& bb, const Ray& ray) {
   const f16v k = *reinterpret_cast<const f16v*>(&bb);  // centre, a1, a2, r2m, band[0..2]
   const f16v m = *(reinterpret_cast<const f16v*>(&bb) + 1);  // band[3..7]
   const V4 pc = sub(V4{k[0], k[1], k[2], k[3]}, ray.point);
@@ -601,57 +500,12 @@ __device__ __forceinline__ bool far_from(const BoundBall& bb, const Ray& ray, co
   const float dB = fmaf_(u1, u1, u2 * u2), dA = a - dB;  // squared distances to plane B and plane A
   const bool near_surface = (dA >= k[13] && dA <= k[14]) || (dA >= k[15] && dA <= m[0]) ||
                             (dB >= m[1] && dB <= m[2]) || (dB >= m[3] && dB <= m[4]);
-#if RT4_BALL_BEHIND_MAX
-  // the same skip as one v_max: with b clamped at 0 the line test reads a (1 - 4e-6) > R2m when b <= 0, i.e. the origin
+  // both skips as one v_max: with b clamped at 0 the line test reads a (1 - 4e-6) > R2m when b <= 0, i.e. the origin
   // outside the inflated ball (a finite b: a, l2 < 1e30)
-  if constexpr (BEHIND && !OCC && LINE) {
-    const float bp = fmaxf(b, 0.0f);
-    return !near_surface && a < 1e30f && l2 > 1e-30f && l2 < 1e30f && (a - fmaf_(4e-6f, a, k[12])) * l2 > bp * bp;
-  }
-#endif
-  const bool behind = BEHIND && b <= 0.0f && a > k[12];
-  if constexpr (!OCC && LINE)  // r06-v53's expression as it was (the same code in the kernels without the knob)
-    return !near_surface && a < 1e30f && l2 > 1e-30f && l2 < 1e30f && ((a - fmaf_(4e-6f, a, k[12])) * l2 > b * b || behind);
-  const bool in_range = a < 1e30f && l2 > 1e-30f && l2 < 1e30f;
-  bool occ = false;
-  if constexpr (OCC) {  // RT4_OCCLUDE_SKIP (below): the ball starts beyond acc's hit
-    const float x = b - acc->dist * l2 - 5e-5f * (a + l2);
-    occ = acc->hit && x > 0.0f && x * x > k[12] * l2;
-  }
-  return in_range && ((LINE && !near_surface && ((a - fmaf_(4e-6f, a, k[12])) * l2 > b * b || behind)) || occ);
-}
-
-// Hypercube skip behind a hit (round 6, RT4_HYPER_SKIP, A/B knob): the hypercube's finite hits lie on its cells, inside
-// hyper_bound's inflated ball; its +inf (parallel face) and NaN hits never replace a hit with a finite distance. So when
-// acc already holds such a hit and the ray's line clears the ball, or the ball is behind the ray (the max(b, 0) form),
-// the hypercube cannot change acc and its test is skipped.
-#ifndef RT4_HYPER_SKIP
-#define RT4_HYPER_SKIP 0
-#endif
-__device__ __forceinline__ bool hyper_skip(const BoundBall& bb, const Ray& ray, const Cand& acc) {
-  const f16v k = *reinterpret_cast<const f16v*>(&bb);
-  const V4 pc = sub(V4{k[0], k[1], k[2], k[3]}, ray.point);
-  const float a = dot(pc, pc), b = dot(pc, ray.drct), l2 = dot(ray.drct, ray.drct);
   const float bp = fmaxf(b, 0.0f);
-  return acc.hit && acc.dist < 3.0e38f && a < 1e30f && l2 > 1e-30f && l2 < 1e30f &&
-         (a - fmaf_(4e-6f, a, k[12])) * l2 > bp * bp;
+  return !near_surface && a < 1e30f && l2 > 1e-30f && l2 < 1e30f && (a - fmaf_(4e-6f, a, k[12])) * l2 > bp * bp;
 }
 
-// Occlusion skip (round 6, RT4_OCCLUDE_SKIP: 1 = tiger and union, 3 = also the hypercube): a group whose bounding ball
-// starts beyond the closest hit so far cannot change it. Every hit the group's exact test reports lies in the inflated
-// ball (rt4_aux.h BoundBall; the hypercube's finite hits lie on its cells' faces, inside hyper_bound), so its distance
-// t satisfies t l2 >= b - sqrt(R2m l2) (b = (c - p).d, l2 = |d|^2), and closest() keeps acc for any t >= acc.dist
-// (ties keep acc; NaN and +inf distances never replace a hit). The test skips when
-//   x = b - acc.dist l2 - 5e-5 (a + l2) > 0  and  x^2 > R2m l2,
-// where 5e-5 (a + l2) >= 1e-4 sqrt(a l2) covers the fp32 rounding of b, of the products and of the hit point itself
-// (each ~1e-6 sqrt(a l2)). acc without a hit, or with a NaN or infinite distance, never skips.
-#ifndef RT4_OCCLUDE_SKIP
-#define RT4_OCCLUDE_SKIP 0
-#endif
-template <uint32_t SH>
-constexpr bool occlude_of(int what) {  // what: 1 = tiger / union, 2 = hypercube; not in the closed rooms' kernels
-  return (RT4_OCCLUDE_SKIP & what) != 0 && ((SH >> 8) & 0xFFu) < 4;
-}
 // Flat primitive-table index of each group's first entry (rt4_aux.h SceneAux::prims order): compile-time
 // for exact-count shapes (the scene-shape check pins one union / hypercube / tiger), else read.
 struct PrimBases {
@@ -672,8 +526,8 @@ __device__ __forceinline__ PrimBases prim_bases(const SceneAux* __restrict__ X) 
   }
 }
 
-// find_cand in three parts, so that a kernel can pool the exact sphere tests of several waves between
-// them (rt4_trace.hip, POOL): find_pre = the spaces and the sphere cull (pending-sphere bit mask),
+// find_cand in three parts, so that a kernel can defer a lane's exact sphere tests between them
+// (rt4_trace.hip, DEFER): find_pre = the spaces and the sphere cull (pending-sphere bit mask),
 // sphere_exact = one pending sphere's exact test, find_rest = the groups after the spheres.
 // Exact-count sphere groups of up to GEO_MAX spheres keep the cull's two dots per sphere for the exact
 // test (sphere_cand_d); RT4_SPHERE_GEO=0 recomputes them from the centre (A/B knob). Measured
@@ -681,9 +535,6 @@ __device__ __forceinline__ PrimBases prim_bases(const SceneAux* __restrict__ X) 
 // trip, 6 live VGPRs) -0.3 %, so three or more spheres keep the recomputation.
 #ifndef RT4_SPHERE_GEO
 #define RT4_SPHERE_GEO 1
-#endif
-#ifndef RT4_CULL_MAX
-#define RT4_CULL_MAX 0
 #endif
 constexpr int GEO_MAX = 2;
 template <uint32_t SH>
@@ -723,19 +574,7 @@ __device__ __forceinline__ Cand find_pre(const rt4_scene_desc* __restrict__ S, c
 #ifdef RT4_CULL_BITWISE  // A/B build only: the same predicate without short-circuit branches
       const bool skip = outside & ((dp < 0.0f) | (d2 - dp * dp > fmaf_(SPHERE_CULL_K, d2, k[5])));
 #else
-      bool skip;
-      if constexpr (RT4_CULL_MAX && !(K & K_TIGER)) {
-        // round 6 (A/B knob; not next to a tiger, where it spilled): dp clamped at 0 folds the "outside and pointing
-        // away" early-out into the one test: for dp < 0 it reads d2 > fma(K, d2, r2m) > r^2 (1 + 1e-4), so len_po >= r
-        // and the exact path's own early-out (:205) returns no hit; outside rays nearer the surface than that now run
-        // the exact path, which returns the same no hit; inside rays are never culled (d2 < r^2 < the threshold); a NaN
-        // dp stays NaN (a select, not max), so such rays are not culled, as before.
-        (void)outside;
-        const float bp = dp < 0.0f ? 0.0f : dp;
-        skip = d2 - bp * bp > fmaf_(SPHERE_CULL_K, d2, k[5]);
-      } else {
-        skip = outside && (dp < 0.0f || d2 - dp * dp > fmaf_(SPHERE_CULL_K, d2, k[5]));
-      }
+      const bool skip = outside && (dp < 0.0f || d2 - dp * dp > fmaf_(SPHERE_CULL_K, d2, k[5]));
 #endif
       pend |= skip ? 0u : (1u << i);
     });
@@ -794,14 +633,12 @@ __device__ __forceinline__ Cand find_rest(const rt4_scene_desc* __restrict__ S, 
 #endif
     });
   if (K & K_UNION)
-    if (!(RT4_BOUND_SKIP && far_from<ball_behind_of<SH>(), occlude_of<SH>(1)>(X->union_bound[0], ray, &inter)))
+    if (!(RT4_BOUND_SKIP && far_from(X->union_bound[0], ray)))
       inter = closest(union_cand(S, X, 0, B.uni, ray), inter);
   if (K & K_HYPERCUBE)
-    if (!(occlude_of<SH>(2) && far_from<false, true, false>(X->hyper_bound[0], ray, &inter)) &&
-        !(RT4_HYPER_SKIP && hyper_skip(X->hyper_bound[0], ray, inter)))
-      inter = closest(hypercube_cand<RT4_HYPER_PENDING != 0, RT4_HYPER_AXIS && (RT4_HYPER_AXIS_TIGER || !(K & K_TIGER))>(S, X, reinterpret_cast<const float4*>(P) - HYPER_CELLS_LDS, 0, B.cube, ray), inter);
+    inter = closest(hypercube_cand(S, X, reinterpret_cast<const float4*>(P) - HYPER_CELLS_LDS, 0, B.cube, ray), inter);
   if ((K & K_TIGER) && WITH_TIGER)
-    if (!(RT4_BOUND_SKIP && far_from<ball_behind_of<SH>(), occlude_of<SH>(1)>(X->tiger_bound[0], ray, &inter))) {
+    if (!(RT4_BOUND_SKIP && far_from(X->tiger_bound[0], ray))) {
 #ifdef RT4_LANESTATS  // diagnostic: tiger tests and their active lanes (counter[60], [61])
       {
         const unsigned long long ex = __builtin_amdgcn_read_exec();
@@ -816,11 +653,11 @@ __device__ __forceinline__ Cand find_rest(const rt4_scene_desc* __restrict__ S, 
   return inter;
 }
 
-// The exact tests of a lane's pending spheres in index order (pass 2 of find_cand), from the cull's dots
-// or the centre.
-template <uint32_t SH, bool GEO = true>
+// The exact tests of a lane's pending spheres in index order (pass 2 of find_cand), from the centre: the
+// deferred-sphere kernel does not keep the cull's dots (rt4_trace.hip, LSUM_REG).
+template <uint32_t SH>
 __device__ __forceinline__ Cand exact_pending(const SceneAux* __restrict__ X, const PrimEntry* P, const Ray& ray,
-                                              const SphereGeo& geo, uint32_t pend, Cand inter) {
+                                              uint32_t pend, Cand inter) {
   while (pend) {
 #ifdef RT4_LANESTATS  // diagnostic: trips and their active lanes (counter[40], [41]), as in find_cand
     {
@@ -833,10 +670,7 @@ __device__ __forceinline__ Cand exact_pending(const SceneAux* __restrict__ X, co
 #endif
     const int i = __builtin_ctz(pend);
     pend &= pend - 1u;
-    if constexpr (GEO && geo_spheres<SH>() > 0)
-      inter = closest(sphere_exact_geo<SH>(X, P, geo, i), inter);
-    else
-      inter = closest(sphere_exact<SH>(X, P, ray, i), inter);
+    inter = closest(sphere_exact<SH>(X, P, ray, i), inter);
   }
   return inter;
 }

@@ -73,40 +73,16 @@ namespace {
 // 1 = also the tiger kernels, 2 = every kernel, 0 = none (A/B knob; profiles/r03_ab.txt).
 #define RT4_PHASE_REFILL 3
 #endif
-#ifndef RT4_LUT_PREFETCH
-// When the sampler-table entry of a possible diffuse bounce is fetched: 2 = at a hit, in flight
-// during resolve + shading; 0 = in rand_drct. Measured alternatives, all slower (profiles/r01_ab.txt):
-// at the top of every iteration; at the top for lanes that can hit; at a hit by LDS-DMA.
-#define RT4_LUT_PREFETCH 2
-#endif
 #ifndef RT4_SKY_THRESHOLD
 #define RT4_SKY_THRESHOLD 1
 #endif
 using WEntry = float;  // a {w, sqrt(1 - w*w)} table was 1 % faster on sphere, 6 % slower on room (rejected)
-#ifndef RT4_ABL_WLUT_STRIDE
-// A/B build only (RT4_ABL_WLUT_STRIDE=16: one entry per 64-B line, a 512 MiB table that cannot stay in
-// the 256 MiB Infinity Cache): where the gathers are served from (profiles/r03_ab.txt)
-#define RT4_ABL_WLUT_STRIDE 1
-#endif
 __device__ __forceinline__ float went_w(WEntry e) { return e; }
 #ifndef RT4_ORDER_PREPASS
 #define RT4_ORDER_PREPASS 1  // longest-first tile order from a primary-ray pre-pass (rt4_tile_order_kernel)
 #endif
-#ifndef RT4_LAST_FRAME_ORDER
-// The tile order of a pipelined launch's last frame (round 6, A/B knob): 0 = row-major like the other frames; 1 = its
-// rows in reverse (bottom-up: in the reference's scenes the sky is at the top, so the cheapest tiles go last); 2 = the
-// pre-pass's hit-first order (§4.15) for the last frame only. Only the launch's drain depends on the last frame's
-// order; images and counts do not.
-#define RT4_LAST_FRAME_ORDER 0
-#endif
 #ifndef RT4_SKY_PRETEST
 #define RT4_SKY_PRETEST 1
-#endif
-#ifndef RT4_POOL_SPHERES
-// Cross-wave pooling of the exact sphere tests (rt4_trace_kernel POOL). Bit-exact, but measured
-// slower: sphere -13 %, room -7 %, all_primitives -21 % (profiles/r02_ab.txt): the four waves must
-// iterate in step, and two barriers per iteration cost more than the denser tests save. Off.
-#define RT4_POOL_SPHERES 0
 #endif
 #ifndef RT4_CLAIM_TILES
 #define RT4_CLAIM_TILES 4  // 8x8 tiles per queue atomic in pipelined launches (rt4_trace_kernel CLAIM_TILES)
@@ -123,12 +99,6 @@ __device__ __forceinline__ float went_w(WEntry e) { return e; }
 #ifndef RT4_TIGER_SPLIT
 #define RT4_TIGER_SPLIT 16  // in-wave split of the tiger test in the lockstep kernels: the most lanes split (0 = off)
 #endif
-#ifndef RT4_REFILL_HYPER
-#define RT4_REFILL_HYPER 0  // the refill threshold of the open hypercube kernels (0: RT4_REFILL_MIN_OPEN; A/B knob)
-#endif
-#ifndef RT4_SAVE_HYPER
-#define RT4_SAVE_HYPER 0  // the tiger kernels' register savings (RT4_WAVE_COUNT, RT4_FLUSH_REMAT) in the hypercube kernels
-#endif
 #ifndef RT4_REFILL_OPEN_TIGER
 #define RT4_REFILL_OPEN_TIGER 2  // the refill threshold of the open tiger kernels (0: REFILL_MIN): config 5 +0.6 % at 2
                                  // (3: +0.3 %, 4: +0.25 %; r05-v51, profiles/r05_ab.txt)
@@ -136,33 +106,8 @@ __device__ __forceinline__ float went_w(WEntry e) { return e; }
 #ifndef RT4_TIGER_SPLIT_REUSE
 #define RT4_TIGER_SPLIT_REUSE 1  // the split in the lockstep kernels' primary-reuse instantiations too
 #endif
-#ifndef RT4_TIGER_SPLIT_OPEN_LDS
-// round 6 (A/B knob): the open tiger kernels split through the mirror room's LDS hand-off after the deferral decides
-// to run (at most RT4_TIGER_SPLIT_OPEN lanes split, more run the direct test) instead of serving over ds_bpermute
-#define RT4_TIGER_SPLIT_OPEN_LDS 0
-#endif
-#ifndef RT4_TIGER_SPLIT_BPERM_RES
-// round 6 (A/B knob): the split's quarter results go back to their owners by ds_bpermute instead of the per-wave LDS
-// area (no lds_tres), so the open kernels' split fits the all_primitives kernel's LDS at 6 blocks per CU
-#define RT4_TIGER_SPLIT_BPERM_RES 0
-#endif
-#ifndef RT4_TIGER_SPLIT_OPEN
-#define RT4_TIGER_SPLIT_OPEN 0  // the same in the open tiger kernels (tiger, all_primitives)
-#endif
-#ifndef RT4_BEAT_SLACK
-#define RT4_BEAT_SLACK 0  // in-beat tiger deferral in the lockstep kernels: parked iterations per sample (0 = off)
-#endif
 #ifndef RT4_DEFER_TIGER_WAIT
 #define RT4_DEFER_TIGER_WAIT 6  // r05-v52: 6 (config 5 +0.4 % over 4 in 5 rounds; 3 and 12 slower; profiles/r05_ab.txt)
-#endif
-#ifndef RT4_DEFER_EXACT_TIGER
-// Deferred exact sphere tests in the open tiger kernels (round 6; rt4_trace_kernel SDEFER): the
-// wave's pending-lane threshold (0 = off) and the most iterations a lane waits. A lane whose sphere cull leaves
-// pending spheres parks before any other group and redoes the cull next iteration (no state kept), as in §4.25.
-#define RT4_DEFER_EXACT_TIGER 0
-#endif
-#ifndef RT4_DEFER_WAIT_TIGER
-#define RT4_DEFER_WAIT_TIGER 4
 #endif
 #ifndef RT4_DEFER_EXACT
 // Deferred exact sphere tests: a wave runs its pending exact sphere tests only once at
@@ -191,12 +136,6 @@ __device__ __forceinline__ float went_w(WEntry e) { return e; }
 #endif
 #ifndef RT4_OVERLAP_FRAMES
 #define RT4_OVERLAP_FRAMES 1  // single-frame launches overlap the previous frame's drain
-#endif
-#ifndef RT4_DEFER_GEO
-#define RT4_DEFER_GEO 0  // the deferred-sphere kernel keeps the cull's dots for the exact tests (r03: 1)
-#endif
-#ifndef RT4_REFILL_ONE_TRIP
-#define RT4_REFILL_ONE_TRIP 1
 #endif
 #ifndef RT4_OVERLAP_GRID_LESS
 // Overlapped traces of short frames (at most RT4_OVERLAP_SHORT_WORK pixel samples x (bounces + 1)) run this many
@@ -236,7 +175,7 @@ static_assert(RT4_OVERLAP_BIG >= 2 && RT4_OVERLAP_BIG <= RT4_OVERLAP_SLOTS, "ove
 #define RT4_WAVES_MIRROR 6  // the tiger kernel specialised for three or more spaces (config 4's mirror room)
 #endif
 #ifndef RT4_WAVES_MIRROR_INLINE
-#define RT4_WAVES_MIRROR_INLINE 6  // the same with the inline Newton sampler (5 with RT4_TIGER_CULL: one spill at 6)
+#define RT4_WAVES_MIRROR_INLINE 6  // the same with the inline Newton sampler
 #endif
 #ifndef RT4_WAVES_MIRROR_REUSE
 #define RT4_WAVES_MIRROR_REUSE 5  // its primary-reuse instantiations (spilled in the loop at 6)
@@ -254,7 +193,7 @@ static_assert(RT4_OVERLAP_BIG >= 2 && RT4_OVERLAP_BIG <= RT4_OVERLAP_SLOTS, "ove
 #define RT4_WAVES_UNION_REUSE 5  // the cylinders-union kernel's primary-reuse instantiation (spilled at 6)
 #endif
 #ifndef RT4_WAVES_SPHERE
-#define RT4_WAVES_SPHERE 7  // r04: 7 with the light sum in LDS and no kept cull dots (RT4_DEFER_GEO 0)
+#define RT4_WAVES_SPHERE 7  // r04: 7 with the light sum in LDS and no kept cull dots
 #endif
 #ifndef RT4_WAVES_EXACT
 #define RT4_WAVES_EXACT 6  // exact-count kernels without a tiger (sphere, room, hypercube, cylinder4d): 6 waves/SIMD
@@ -391,26 +330,19 @@ __device__ __forceinline__ uint32_t rand_bits(RngState& r) {  // 23 mantissa bit
 __device__ __forceinline__ float bits_to_rand(uint32_t m) { return __uint_as_float(m | 0x3F800000u) - 1.0f; }  // :117
 __device__ __forceinline__ float rand_(RngState& r) { return bits_to_rand(rand_bits(r)); }
 
-#if RT4_LUT_PREFETCH
 // Index of the sampler-table entry a diffuse bounce reads once rand_outcome's draw is consumed: the
 // next rand() call (rand_drct's w, shader.frag:154). Pure function of the counter.
 __device__ __forceinline__ uint32_t next_w_index(const RngState& r) {
   return hash_u32(r.base ^ (r.iter + 0x79A010A9u)) & 0x007FFFFFu;
 }
-#endif
 
-// w_pre: wlut[next_diffuse_w_index()] loaded at the top of the iteration (LUT path only)
+// w_pre: wlut[next_w_index()], fetched at the hit (shade(); LUT path only)
 template <bool LUT>
-__device__ __forceinline__ V4 rand_drct(RngState& rng, const WEntry* __restrict__ wlut, WEntry w_pre) {  // :153-158
+__device__ __forceinline__ V4 rand_drct(RngState& rng, WEntry w_pre) {  // :153-158
   float w, r;
   if (LUT) {
-#if RT4_LUT_PREFETCH
     rng.iter += 0x79A010A9u;  // the w draw: its value was prefetched
-    const WEntry e = w_pre;
-#else
-    const WEntry e = wlut[rand_bits(rng) * RT4_ABL_WLUT_STRIDE];
-#endif
-    w = went_w(e);
+    w = went_w(w_pre);
     r = sqrt_(1.0f - w * w);
   } else {
     w = w_by_volume(rand_(rng), nullptr);
@@ -613,35 +545,17 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
   }
   const PrimEntry* P = reinterpret_cast<const PrimEntry*>(lds_prims + CELLS4);
 
-  // Cross-wave pooling of the exact sphere tests: in the specialised kernels with
-  // spheres, the four waves of a workgroup iterate in step; each iteration every wave publishes the
-  // rays of its lanes with pending spheres (find_pre's cull) and the (lane, sphere) pairs, and after a
-  // barrier the workgroup's 256 lanes evaluate the pooled pairs densely (one pair per lane) instead
-  // of each wave running the ~190-instruction test on the ~14 of its 64 lanes that need it. Results
-  // are combined by each ray's own lane in sphere index order (closest(), shader.frag:440-441), so
-  // the bits do not change. Up to PCAP lanes per wave are pooled; the rest test their spheres locally.
-  constexpr bool POOL = RT4_POOL_SPHERES && K != GENERIC && (K & K_SPHERES) && sh_count(K, 2) != 0;
-  constexpr int NSH = POOL ? static_cast<int>(sh_count(K, 2)) - 1 : 1;
-  constexpr int PCAP = 32, QCAP = POOL ? PCAP * NSH : 1;
-  __shared__ float4 lds_pray[POOL ? 4 * PCAP * 2 : 1];  // pooled rays: {point, drct} per slot
-  __shared__ uint16_t lds_pair[POOL ? 4 * QCAP : 1];   // slot | sphere << 6
-  __shared__ float2 lds_pres[POOL ? 4 * QCAP : 1];     // {dist, hit | flip << 1}
-  __shared__ uint4 lds_pn4;                            // pairs of each wave | busy << 31, one word per wave
-  uint32_t* const lds_pn = reinterpret_cast<uint32_t*>(&lds_pn4);
-  const unsigned wave = threadIdx.x >> 6;
   // Deferred exact sphere tests (A/B knob RT4_DEFER_EXACT = the wave's pending-lane threshold, 0 = off;
   // RT4_DEFER_WAIT = the most iterations a parked lane waits): DESIGN.md §9, profiles/r03_ab.txt
   // (not in the native-math build: the deferral runs find_pre's cull, whose exactness bound assumes the
   // deterministic fused dot that build un-fuses)
-  constexpr bool DEFER = RT4_SPHERE_CULL && RT4_DEFER_EXACT > 0 && !POOL && !REUSE && K != GENERIC && (K & K_SPHERES) && !(K & K_TIGER) &&
+  constexpr bool DEFER = RT4_SPHERE_CULL && RT4_DEFER_EXACT > 0 && !REUSE && K != GENERIC && (K & K_SPHERES) && !(K & K_TIGER) &&
                          !phase_refill_of(K) && sh_count(K, 2) != 0;
   constexpr bool PHASE = phase_refill_of(K);
   constexpr unsigned REFILL_K =
       K != GENERIC && (K >> 8) != 0 && !PHASE && !REUSE && (RT4_REFILL_OPEN_TIGER > 0 || !(K & K_TIGER))
-          ? static_cast<unsigned>((K & K_TIGER) ? RT4_REFILL_OPEN_TIGER
-                                                : ((K & K_HYPERCUBE) && RT4_REFILL_HYPER > 0 ? RT4_REFILL_HYPER
-                                                                                              : RT4_REFILL_MIN_OPEN))
-                                                                          : REFILL_MIN;
+          ? static_cast<unsigned>((K & K_TIGER) ? RT4_REFILL_OPEN_TIGER : RT4_REFILL_MIN_OPEN)
+          : REFILL_MIN;
   int defer_age = 0;  // wave-uniform: iterations since the wave's parked lanes were first parked
   // Wave clock (closed scenes): while almost every path of the wave runs all R + 1 bounces
   // (early ends <= 1/32 of the sample ends, a leaky count), samples start only every R + 1 iterations, so
@@ -655,38 +569,19 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
   // bounding ball keeps its candidate of every other group (cold[512], pack_cand) and waits until at least
   // RT4_DEFER_TIGER lanes of the wave need the tiger test, or RT4_DEFER_TIGER_WAIT iterations; then the
   // tiger runs last, as in find_rest (closest(tiger, the rest): the same bits).
-  // In-beat deferral (RT4_BEAT_SLACK = D > 0): the lockstep kernels defer too, with the wave
-  // clock's period stretched to R + 1 + D iterations and each lane allowed at most D parked iterations per sample,
-  // so a lane that parks still ends its sample within the period and keeps the beat.
-  constexpr int BEAT_SLACK = PHASE && CLOCK ? RT4_BEAT_SLACK : 0;
-  constexpr bool TDEFER = RT4_DEFER_TIGER > 0 && !REUSE && K != GENERIC && (K & K_TIGER) && (!PHASE || BEAT_SLACK > 0);
-  int slack = BEAT_SLACK;            // BEAT_SLACK: the lane's parked iterations left in this sample
-  // Deferred exact sphere tests next to the deferred tiger (RT4_DEFER_EXACT_TIGER > 0): the open tiger kernels with
-  // spheres (all_primitives, BASELINE config 5) split find_cand<K, false> into find_pre (spaces + sphere cull), the
-  // pending exact tests and find_rest without the tiger, the same ops in the same order; a lane with pending spheres
-  // parks until RT4_DEFER_EXACT_TIGER lanes of the wave have some, or RT4_DEFER_WAIT_TIGER iterations (defer_age).
-  constexpr bool SDEFER = RT4_DEFER_EXACT_TIGER > 0 && RT4_SPHERE_CULL && TDEFER && !PHASE && !REUSE && K != GENERIC &&
-                          (K & K_SPHERES) && sh_count(K, 2) != 0;
+  constexpr bool TDEFER = RT4_DEFER_TIGER > 0 && !REUSE && K != GENERIC && (K & K_TIGER) && !PHASE;
   // In-wave split of the tiger test (RT4_TIGER_SPLIT = the most lanes split, 0 = off): when at
   // most that many lanes of the wave need the tiger test in an iteration, each one's test is cut into its four
   // (axes pair, radius) quarters (rt4_fast.h tiger_quarter), run on four lanes at once through a per-wave LDS
-  // hand-off, and folded back in tiger_cand's order: the same bits, on up to 4x the lanes. Lockstep kernels (the
-  // mirror room, where lanes may not park for a deferral) and, with RT4_TIGER_SPLIT_OPEN, the open ones.
-  // (with primary reuse only in the lockstep kernels: a lane whose bounce 0 comes from the cache takes no part)
-  constexpr bool TSPLIT = (!REUSE || (CLOCK && RT4_TIGER_SPLIT_REUSE)) && K != GENERIC && (K & K_TIGER) &&
-                          (PHASE ? RT4_TIGER_SPLIT > 0 : RT4_TIGER_SPLIT_OPEN > 0);
-  constexpr unsigned TSPLIT_MAX = PHASE ? RT4_TIGER_SPLIT : RT4_TIGER_SPLIT_OPEN;
-  // Open tiger kernels (TDEFER and TSPLIT): a run serves at most TSPLIT_MAX lanes, the parked ones first, and the
-  // others stay parked, so every test runs split and the direct test is not compiled. Their rays and results move by
-  // ds_bpermute (no LDS buffer: the all_primitives kernel's LDS allows no more at 6 blocks per CU). Bit-exact
-  // (tools/variant_probe.py) but rejected (profiles/r05_ab.txt, r05-v48 trial): the per-lane pair geometry takes
-  // ~40 VGPRs, so the kernel spills at 6 waves and runs 5 (-6.9 % config 5, 20 B spill) or 4 (-12 %, no spill).
-  constexpr bool TSERVE = TSPLIT && TDEFER && !PHASE && !RT4_TIGER_SPLIT_OPEN_LDS;
+  // hand-off, and folded back in tiger_cand's order: the same bits, on up to 4x the lanes. Lockstep kernels only
+  // (the mirror room, where lanes may not park for a deferral).
+  // (with primary reuse a lane whose bounce 0 comes from the cache takes no part)
+  constexpr bool TSPLIT = (!REUSE || (CLOCK && RT4_TIGER_SPLIT_REUSE)) && K != GENERIC && (K & K_TIGER) && PHASE &&
+                          RT4_TIGER_SPLIT > 0;
+  constexpr unsigned TSPLIT_MAX = RT4_TIGER_SPLIT;
   static_assert(!TSPLIT || TSPLIT_MAX <= 16, "one pass of four quarters per test");
-  constexpr bool TRES_LDS = TSPLIT && !TSERVE && !(RT4_TIGER_SPLIT_BPERM_RES && !PHASE);
-  __shared__ float4 lds_tray[TSPLIT && !TSERVE ? 4 * 2 * TSPLIT_MAX : 1];  // per wave: up to TSPLIT_MAX rays {point, drct}
-  __shared__ float4 lds_tres[TRES_LDS ? 4 * 4 * TSPLIT_MAX : 1];  // per wave: 4 quarter results per test (pack_cand)
-  __shared__ uint32_t lds_town[TSERVE ? 4 * 16 : 1];            // per wave: the lane of each served test
+  __shared__ float4 lds_tray[TSPLIT ? 4 * 2 * TSPLIT_MAX : 1];  // per wave: up to TSPLIT_MAX rays {point, drct}
+  __shared__ float4 lds_tres[TSPLIT ? 4 * 4 * TSPLIT_MAX : 1];  // per wave: 4 quarter results per test (pack_cand)
   bool tparked = false;              // TDEFER: the lane waits for the tiger test with its candidate in cold[512]
   int tdefer_age = 0;                // TDEFER, wave-uniform
   auto clock_on = [&]() { return n_early * 32u <= n_full; };
@@ -707,9 +602,9 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
   // round trip. Measured (profiles/r02_ab.txt): sphere scene +1.2 %; the hypercube kernel -2.6 % (same
   // 6 waves/SIMD, worse allocation); the tiger kernels have no VGPRs to spare at their wave bounds.
   // (not in the deferred-sphere kernel since r04: its light sum in LDS and the exact tests recomputing the
-  // cull's dots (DEFER_GEO) bring it to 72 VGPRs, 7 waves/SIMD with no spill in the loop: config 2 +3-4 %,
+  // cull's dots bring it to 72 VGPRs, 7 waves/SIMD with no spill in the loop: config 2 +3-4 %,
   // profiles/r04_ab.txt)
-  constexpr bool LSUM_REG = (RT4_LSUM_REG && K != GENERIC && !(K & (K_TIGER | K_HYPERCUBE)) && !(DEFER && !RT4_DEFER_GEO)) ||
+  constexpr bool LSUM_REG = (RT4_LSUM_REG && K != GENERIC && !(K & (K_TIGER | K_HYPERCUBE)) && !DEFER) ||
                             (RT4_LSUM_REG_TIGER && K != GENERIC && (K & K_TIGER) && !REUSE && min_waves_of(K, REUSE, LUT) <= 5);
   float4 lsum_reg = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   auto lsum_load = [&]() -> float4 {
@@ -736,7 +631,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
   // wave's first thread from a scalar register and the lane from mbcnt where it runs, so no VGPR keeps them (or their
   // LDS addresses) live across the tiger test, the loop's register peak; there they were spilled. The sphere and
   // hypercube kernels measured 1.4 % / 5.7 % slower with it (profiles/r05_ab.txt) and keep the plain form.
-  constexpr bool REMAT = RT4_FLUSH_REMAT && K != GENERIC && ((K & K_TIGER) || (RT4_SAVE_HYPER && (K & K_HYPERCUBE)));
+  constexpr bool REMAT = RT4_FLUSH_REMAT && K != GENERIC && (K & K_TIGER);
   const unsigned wave_s = __builtin_amdgcn_readfirstlane(wbase);
   unsigned in_next = 64;  // wave-uniform: next inbox entry to hand out (64: empty)
   // RT4_CLAIM_TILES > 1: one atomic claims that many consecutive tiles; the spare ones are used in turn.
@@ -755,7 +650,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
   // Without primary reuse every counted call is evaluated and a lane adds at most one per iteration: the wave
   // counts them in a wave-uniform (scalar) register from one ballot per iteration instead of a VGPR per lane,
   // which frees a register in the register-bound tiger kernels (RT4_WAVE_COUNT).
-  constexpr bool WAVE_COUNT = RT4_WAVE_COUNT && !REUSE && K != GENERIC && ((K & K_TIGER) || (RT4_SAVE_HYPER && (K & K_HYPERCUBE)));
+  constexpr bool WAVE_COUNT = RT4_WAVE_COUNT && !REUSE && K != GENERIC && (K & K_TIGER);
   unsigned long long w_inter = 0;
 
 #ifdef RT4_LANESTATS
@@ -847,9 +742,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
       pos -= frame * a.frame_tiles;
       in_seed = static_cast<uint32_t>(a.frame_seed[frame]);
     }
-    const bool last = a.n_frames <= 1 || frame + 1u == static_cast<unsigned>(a.n_frames);  // wave-uniform
-    if (RT4_LAST_FRAME_ORDER == 1 && a.n_frames > 1 && last && a.n_jobs == 1) pos = a.frame_tiles - 1u - pos;
-    const unsigned btile = order && (RT4_LAST_FRAME_ORDER != 2 || last) ? order[pos] : pos;
+    const unsigned btile = order ? order[pos] : pos;
     const int job = (a.n_jobs > 1 && btile >= a.jobs[1].tile_base) + (a.n_jobs > 2 && btile >= a.jobs[2].tile_base);
     const JobArgs& J = a.jobs[job];
     const unsigned tile = btile - J.tile_base;
@@ -891,13 +784,10 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
     // rand_outcome's draw first (shader.frag:488, :121; the same draw, taken earlier): only a
     // diffuse outcome reads the sampler table, so mirrors and reflect outcomes issue no gather
     const bool diffuse = rand_(rng) > Finder<K>::refl(S, P, c);
-#if RT4_LUT_PREFETCH == 2
-#ifdef RT4_ABL_NOLUT  // ablation only (wrong images): the index arithmetic without the table gather
-    if (LUT && diffuse) w_pre = WEntry{static_cast<float>(next_w_index(rng)) * 2.3841858e-7f - 1.0f};
-#else
-    if (LUT && diffuse) w_pre = wlut[next_w_index(rng) * RT4_ABL_WLUT_STRIDE];  // in flight during resolve + shading
-#endif
-#endif
+    // the entry is fetched here, in flight during resolve + shading. Measured alternatives, all slower
+    // (profiles/r01_ab.txt): in rand_drct; at the top of every iteration; at the top for lanes that can hit; at a
+    // hit by LDS-DMA.
+    if (LUT && diffuse) w_pre = wlut[next_w_index(rng)];
     RT4_STAMP(t_ph);
     const Hit h = Finder<K>::resolve(P, ray, c);
     float glow, refl;
@@ -914,7 +804,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
     } else {  // :491 redirect(rand_drct(), norm)
       RT4_LS(6);
       RT4_STAMP(t_ph);
-      const V4 v = rand_drct<LUT>(rng, wlut, w_pre);
+      const V4 v = rand_drct<LUT>(rng, w_pre);
       RT4_ACC(4, t_ph);
       const float dv = dot(v, h.norm);
       ray.drct = dv >= 0.0f ? v : mad(h.norm, -(2.0f * dv), v);
@@ -932,7 +822,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
         if (__ballot(active) == 0ull) wave_it = 0;  // nothing in flight: this iteration starts the period
         boundary = wave_it == 0u;
       }
-      wave_it = wave_it + 1u == static_cast<unsigned>(R + 1 + BEAT_SLACK) ? 0u : wave_it + 1u;
+      wave_it = wave_it + 1u == static_cast<unsigned>(R + 1) ? 0u : wave_it + 1u;
       if (boundary) hold = false;
     }
     if (!exhausted) {
@@ -965,16 +855,11 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
           const unsigned n = min(nidle - got, 64u - in_next);
           if (!active && rank >= got && rank < got + n) {
             const unsigned e = wbase + in_next + (rank - got);
-            // both reads before the test: one LDS round trip per hand-out instead of two (RT4_REFILL_ONE_TRIP)
+            // both reads before the test: one LDS round trip per hand-out instead of two
             const uint2 px = lds_in_px[e];
-#if RT4_REFILL_ONE_TRIP
             const float4 d0 = lds_in_d0[e];
             asm volatile("" ::"v"(d0.x), "v"(d0.y), "v"(d0.z), "v"(d0.w));  // keep the read here, beside px's
-#endif
             if (px.y != 0xFFFFFFFFu) {
-#if !RT4_REFILL_ONE_TRIP
-              const float4 d0 = lds_in_d0[e];
-#endif
               rng = RngState{px.x, in_seed};
               ray = Ray{focus, V4{d0.x, d0.y, d0.z, d0.w}};
               acc = V3{0.0f, 0.0f, 0.0f};
@@ -983,7 +868,6 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
               lsum_store(make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(px.y)));
               s = 0;
               b = 0;
-              if constexpr (BEAT_SLACK > 0) slack = BEAT_SLACK;
               active = NS > 0;
               pending = !active;
             }
@@ -1001,76 +885,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
     typename Finder<K>::R c{};
     bool parked = CLOCK && hold;  // DEFER: the lane's exact sphere tests wait; CLOCK: the lane's next sample
     bool cached = false;          // CLOCK && REUSE: this iteration's candidate came from the primary cache
-    if constexpr (POOL) {
-      // find part 1 + publish; barrier; pooled exact tests; barrier; combine (find part 2 below)
-      RT4_STAMP(t_ph);
-      uint32_t pend = 0;
-      Cand pre = no_cand();
-      if (active) pre = find_pre<K>(S, X, ray, pend);
-      const unsigned long long pm = __ballot(pend != 0u);
-      const unsigned slot = __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(pm >> 32),
-                                                      __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(pm), 0u));
-      const bool pooled = pend != 0u && slot < static_cast<unsigned>(PCAP);
-      if (pooled) {
-        lds_pray[(wave * PCAP + slot) * 2] = make_float4(ray.point.x, ray.point.y, ray.point.z, ray.point.w);
-        lds_pray[(wave * PCAP + slot) * 2 + 1] = make_float4(ray.drct.x, ray.drct.y, ray.drct.z, ray.drct.w);
-      }
-      unsigned nq = 0;  // wave-uniform
-#pragma unroll
-      for (int i = 0; i < NSH; i++) {
-        const unsigned long long qm = __ballot(pooled && ((pend >> i) & 1u));
-        if (pooled && ((pend >> i) & 1u)) {
-          const unsigned q = nq + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(qm >> 32),
-                                                            __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(qm), 0u));
-          lds_pair[wave * QCAP + q] = static_cast<uint16_t>(slot | (static_cast<unsigned>(i) << 6));
-        }
-        nq += static_cast<unsigned>(__popcll(qm));
-      }
-      const bool busy = __any(active) || !exhausted;
-      if (lane == 0) lds_pn[wave] = nq | (busy ? 0x80000000u : 0u);
-      __syncthreads();
-      const uint4 pn = lds_pn4;
-      if (((pn.x | pn.y | pn.z | pn.w) & 0x80000000u) == 0u) break;  // every wave of the block is done
-      const unsigned c1 = pn.x & 0xFFFFu, c2 = c1 + (pn.y & 0xFFFFu), c3 = c2 + (pn.z & 0xFFFFu);
-      const unsigned ntot = c3 + (pn.w & 0xFFFFu);
-      for (unsigned p = threadIdx.x; p < ntot; p += 256u) {
-        const unsigned w = (p >= c1) + (p >= c2) + (p >= c3);
-        const unsigned j = p - (w == 0u ? 0u : (w == 1u ? c1 : (w == 2u ? c2 : c3)));
-        const unsigned e = lds_pair[w * QCAP + j];
-        const unsigned sl = e & 63u;
-        const float4 rp = lds_pray[(w * PCAP + sl) * 2], rd = lds_pray[(w * PCAP + sl) * 2 + 1];
-        const Cand q = sphere_exact<K>(X, P, Ray{V4{rp.x, rp.y, rp.z, rp.w}, V4{rd.x, rd.y, rd.z, rd.w}},
-                                       static_cast<int>(e >> 6));
-        lds_pres[w * QCAP + j] = make_float2(q.dist, __uint_as_float((q.hit ? 1u : 0u) | (q.flip ? 2u : 0u)));
-      }
-      __syncthreads();
-      if (active) {
-        Cand inter = pre;
-        unsigned nb = 0;  // the pair index of this lane's sphere i: recomputed from the same ballots
-#pragma unroll
-        for (int i = 0; i < NSH; i++) {
-          const bool mine = (pend >> i) & 1u;
-          const unsigned long long qm = __ballot(pooled && mine);
-          if (mine) {
-            Cand q;
-            if (pooled) {
-              const unsigned at = nb + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(qm >> 32),
-                                                                 __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(qm), 0u));
-              const float2 r = lds_pres[wave * QCAP + at];
-              const uint32_t f = __float_as_uint(r.y);
-              q = Cand{(f & 1u) != 0u, (f & 2u) != 0u, r.x, r.x, prim_bases<K>(X).sphere + static_cast<uint32_t>(i)};
-              if (!q.hit) q = no_cand();
-            } else {
-              q = sphere_exact<K>(X, P, ray, i);
-            }
-            inter = closest(q, inter);
-          }
-          nb += static_cast<unsigned>(__popcll(qm));
-        }
-        c = find_rest<K>(S, X, P, ray, inter);
-      }
-      RT4_ACC(1, t_ph);
-    } else if constexpr (TDEFER || TSPLIT) {
+    if constexpr (TDEFER || TSPLIT) {
       if (!__any(active)) {
         if (exhausted) break;
         continue;
@@ -1079,7 +894,6 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
       Cand pre = no_cand();
       bool need = false;
       const bool held = CLOCK && parked;  // held for the wave clock (the lockstep kernels)
-      bool fresh = false;                 // SDEFER: the lane starts a find this iteration
       if (active && !held) {
         if constexpr (CLOCK && REUSE) {  // as the generic path below: bounce 0 from the cache at the clock boundary
           cached = use_cached;
@@ -1090,68 +904,21 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
         } else if (tparked) {
           pre = unpack_cand(cold[512]);
           need = true;
-        } else if constexpr (SDEFER) {
-          fresh = true;
         } else {
           pre = find_cand<K, false>(S, X, P, ray);  // every group but the tiger, in order
-          need = !(RT4_BOUND_SKIP && far_from<ball_behind_of<K>(), occlude_of<K>(1)>(X->tiger_bound[0], ray, &pre));
+          need = !(RT4_BOUND_SKIP && far_from(X->tiger_bound[0], ray));
         }
       }
-      if constexpr (SDEFER) {
-        // find_cand<K, false> in its three parts, the pending exact sphere tests deferred (the same bits)
-        uint32_t pend = 0;
-        SphereGeo geo;
-        Cand inter = no_cand();
-        if (fresh) inter = find_pre<K>(S, X, ray, pend, nullptr);
-        const unsigned long long pm = __ballot(pend != 0u);
-        const bool run = pm != 0ull && (static_cast<unsigned>(__popcll(pm)) >= static_cast<unsigned>(RT4_DEFER_EXACT_TIGER) ||
-                                        defer_age >= RT4_DEFER_WAIT_TIGER || pm == __ballot(fresh));
-        if (pm != 0ull && !run) {
-          if (pend != 0u) {
-            parked = true;
-            fresh = false;
-          }
-          ++defer_age;
-        } else {
-          defer_age = 0;
-        }
-        if (fresh) {
-          pre = find_rest<K, false>(S, X, P, ray, exact_pending<K, false>(X, P, ray, geo, pend, inter));
-          need = !(RT4_BOUND_SKIP && far_from<ball_behind_of<K>(), occlude_of<K>(1)>(X->tiger_bound[0], ray, &pre));
-        }
-      }
-      if constexpr (TSERVE) {
-        const unsigned long long mp = __ballot(need && tparked), mn = __ballot(need && !tparked);
-        const unsigned np = static_cast<unsigned>(__popcll(mp)), nt = np + static_cast<unsigned>(__popcll(mn));
-        const bool run = nt != 0u && (nt >= static_cast<unsigned>(RT4_DEFER_TIGER) || tdefer_age >= RT4_DEFER_TIGER_WAIT ||
-                                      (mp | mn) == __ballot(active && !held));
-        const unsigned slot = tparked ? __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mp >> 32),
-                                                                  __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mp), 0u))
-                                      : np + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mn >> 32),
-                                                                       __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mn), 0u));
-        const bool serve = run && need && slot < TSPLIT_MAX;  // the parked lanes first, at most TSPLIT_MAX
-        // every lane's candidate waits in cold[512] (no VGPRs held across the split test)
-        if (active && !held && !tparked) cold[512] = pack_cand(pre);
-        if (need && !serve) {
-          tparked = true;
-          parked = true;
-        }
-        // a run that left lanes parked runs again next iteration; otherwise the deferral's clock
-        tdefer_age = run ? (nt > TSPLIT_MAX ? RT4_DEFER_TIGER_WAIT : 0) : (nt != 0u ? tdefer_age + 1 : 0);
-      } else if constexpr (TDEFER) {
+      if constexpr (TDEFER) {
         const unsigned long long tm = __ballot(need);
-        // in-beat: a lane with no parked iteration left forces the run (its sample must end within the period)
-        const bool forced = BEAT_SLACK > 0 && clock_on() && __ballot(need && slack <= 0) != 0ull;
-        // (!parked: as !held, and it leaves out the lanes parked for their exact sphere tests, SDEFER)
         const bool run = tm != 0ull && (static_cast<unsigned>(__popcll(tm)) >= static_cast<unsigned>(RT4_DEFER_TIGER) ||
-                                        tdefer_age >= RT4_DEFER_TIGER_WAIT || tm == __ballot(active && !parked) || forced);
+                                        tdefer_age >= RT4_DEFER_TIGER_WAIT || tm == __ballot(active && !parked));
         if (tm != 0ull && !run) {
           ++tdefer_age;
           if (need) {
             if (!tparked) cold[512] = pack_cand(pre);
             tparked = true;
             parked = true;
-            if (BEAT_SLACK > 0) --slack;
           }
         } else {
           tdefer_age = 0;
@@ -1171,38 +938,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
         }
       }
 #endif
-      if constexpr (TSERVE) {
-        // every served test split into its quarters; rays and results by ds_bpermute, the owners' lanes by LDS
-        const bool go = active && !parked && need;
-        const unsigned long long gm = __ballot(go);
-        const unsigned ng = static_cast<unsigned>(__popcll(gm));
-        Cand tg = no_cand();
-        if (ng != 0u) {
-          const unsigned ln = rt4_lane_id(), wv = wave_s >> 6;
-          const unsigned rk = __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(gm >> 32),
-                                                        __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(gm), 0u));
-          if (go) lds_town[wv * 16u + rk] = ln;
-          const bool task = ln < 4u * ng;
-          const int src = static_cast<int>((task ? lds_town[wv * 16u + (ln >> 2)] : ln) << 2);
-          auto pull = [&](float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v))); };
-          const Ray tr{V4{pull(ray.point.x), pull(ray.point.y), pull(ray.point.z), pull(ray.point.w)},
-                       V4{pull(ray.drct.x), pull(ray.drct.y), pull(ray.drct.z), pull(ray.drct.w)}};
-          float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-          if (task) q = pack_cand(tiger_quarter(S, X, 0, prim_bases<K>(X).tiger, tr, ln & 3u));
-          auto part = [&](unsigned j) {  // the owner's quarter j, from lane 4 rk + j
-            const int from = static_cast<int>(((go ? 4u * rk + j : ln) & 63u) << 2);
-            return unpack_cand(make_float4(__int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(q.x))),
-                                           __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(q.y))),
-                                           __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(q.z))), 0.0f));
-          };
-          const Cand t01 = closest(part(0u), part(1u));
-          tg = closest(t01, closest(part(2u), part(3u)));
-        }
-        if (active && !parked) {
-          c = go ? closest(tg, unpack_cand(cold[512])) : unpack_cand(cold[512]);
-          tparked = false;
-        }
-      } else if constexpr (TSPLIT) {
+      if constexpr (TSPLIT) {
         const bool go = active && !parked && need;
         Cand tg = no_cand();
         const unsigned long long gm = __ballot(go);
@@ -1214,7 +950,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
           // results (one pass: TSPLIT_MAX <= 16; a loop of passes kept tg live across the quarter and spilled)
           const unsigned ln = rt4_lane_id(), wv = wave_s >> 6;
           float4* const tray = lds_tray + wv * (2u * TSPLIT_MAX);
-          float4* const tres = lds_tres + (TRES_LDS ? wv * (4u * TSPLIT_MAX) : 0u);
+          float4* const tres = lds_tres + wv * (4u * TSPLIT_MAX);
           const unsigned rk = __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(gm >> 32),
                                                         __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(gm), 0u));
           if (go) {
@@ -1224,35 +960,15 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
           // Cross-lane hand-offs through LDS: a wave's LDS accesses complete in program order, and the wave barrier
           // keeps the compiler from moving one lane's read of another lane's slot above the write.
           __builtin_amdgcn_wave_barrier();
-          if constexpr (TRES_LDS) {
-            if (ln < 4u * ng) {  // quarter ln & 3 of the test of the lane ranked ln >> 2
-              const float4 p4 = tray[2u * (ln >> 2)], d4 = tray[2u * (ln >> 2) + 1u];
-              tres[ln] = pack_cand(tiger_quarter(S, X, 0, prim_bases<K>(X).tiger,
-                                                 Ray{V4{p4.x, p4.y, p4.z, p4.w}, V4{d4.x, d4.y, d4.z, d4.w}}, ln & 3u));
-            }
-            __builtin_amdgcn_wave_barrier();
-            if (go)
-              tg = closest(closest(unpack_cand(tres[4u * rk]), unpack_cand(tres[4u * rk + 1u])),
-                           closest(unpack_cand(tres[4u * rk + 2u]), unpack_cand(tres[4u * rk + 3u])));
-          } else {
-            // the owner of rank rk pulls quarter j from lane 4 rk + j (every lane takes part in the permutes; a lane
-            // that owns no test pulls its own value and drops it)
-            float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (ln < 4u * ng) {
-              const float4 p4 = tray[2u * (ln >> 2)], d4 = tray[2u * (ln >> 2) + 1u];
-              q = pack_cand(tiger_quarter(S, X, 0, prim_bases<K>(X).tiger,
-                                          Ray{V4{p4.x, p4.y, p4.z, p4.w}, V4{d4.x, d4.y, d4.z, d4.w}}, ln & 3u));
-            }
-            auto part = [&](unsigned j) {
-              const int from = static_cast<int>(((go ? 4u * rk + j : ln) & 63u) << 2);
-              return unpack_cand(make_float4(__int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(q.x))),
-                                             __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(q.y))),
-                                             __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(q.z))), 0.0f));
-            };
-            const Cand t01 = closest(part(0u), part(1u));
-            const Cand t = closest(t01, closest(part(2u), part(3u)));
-            if (go) tg = t;
+          if (ln < 4u * ng) {  // quarter ln & 3 of the test of the lane ranked ln >> 2
+            const float4 p4 = tray[2u * (ln >> 2)], d4 = tray[2u * (ln >> 2) + 1u];
+            tres[ln] = pack_cand(tiger_quarter(S, X, 0, prim_bases<K>(X).tiger,
+                                               Ray{V4{p4.x, p4.y, p4.z, p4.w}, V4{d4.x, d4.y, d4.z, d4.w}}, ln & 3u));
           }
+          __builtin_amdgcn_wave_barrier();
+          if (go)
+            tg = closest(closest(unpack_cand(tres[4u * rk]), unpack_cand(tres[4u * rk + 1u])),
+                         closest(unpack_cand(tres[4u * rk + 2u]), unpack_cand(tres[4u * rk + 3u])));
         }
         if (active && !parked) {
           c = need ? closest(tg, pre) : pre;
@@ -1273,9 +989,8 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
       }
       RT4_STAMP(t_ph);
       uint32_t pend = 0;
-      SphereGeo geo;
       Cand inter = no_cand();
-      if (active) inter = find_pre<K>(S, X, ray, pend, RT4_DEFER_GEO ? &geo : nullptr);
+      if (active) inter = find_pre<K>(S, X, ray, pend);
       const unsigned long long pm = __ballot(pend != 0u);
       const bool run = pm != 0ull && (static_cast<unsigned>(__popcll(pm)) >= static_cast<unsigned>(RT4_DEFER_EXACT) ||
                                       defer_age >= RT4_DEFER_WAIT || pm == __ballot(active));
@@ -1285,7 +1000,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
       } else {
         defer_age = 0;
       }
-      if (active && !parked) c = find_rest<K>(S, X, P, ray, exact_pending<K, RT4_DEFER_GEO != 0>(X, P, ray, geo, pend, inter));
+      if (active && !parked) c = find_rest<K>(S, X, P, ray, exact_pending<K>(X, P, ray, pend, inter));
       RT4_ACC(1, t_ph);
     } else {
       if (!__any(active)) {
@@ -1332,8 +1047,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
           ray = Ray{focus, V4{c0.x, c0.y, c0.z, c0.w}};
           ++s;
           b = 0;
-          if constexpr (BEAT_SLACK > 0) slack = BEAT_SLACK;
-          acc = V3{0.0f, 0.0f, 0.0f};
+          acc =V3{0.0f, 0.0f, 0.0f};
           T = V3{1.0f, 1.0f, 1.0f};
           if (s >= NS) {
             active = false;
@@ -1442,7 +1156,7 @@ __global__ void rt4_build_wlut_kernel(WEntry* __restrict__ lut) {
   const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= (1u << 23)) return;
   const float w = w_by_volume(__uint_as_float(m | 0x3F800000u) - 1.0f, nullptr);
-  lut[m * RT4_ABL_WLUT_STRIDE] = w;
+  lut[m] = w;
 }
 
 // Checks of the verified-divisor quotient div_c (rt4_fast.h) against the IEEE quotient x / b, one
@@ -2083,8 +1797,6 @@ int build_aux(rt4_context* ctx, const rt4_scene_desc& s, SceneAux* a, char* err,
     const rt4_tiger& t = s.tigers[i];
     const float rs[4] = {t.inner_cyl1.r, t.outer_cyl1.r, t.inner_cyl2.r, t.outer_cyl2.r};
     for (int k = 0; k < 4; k++) a->tiger_r[i][k] = make_divc(rs[k]);
-    const float* cps[4] = {t.inner_cyl1.point, t.outer_cyl1.point, t.inner_cyl2.point, t.outer_cyl2.point};
-    for (int k = 0; k < 4; k++) cull_of(rs[k], cps[k], &a->tiger_cull[i][k]);
     a->tiger_gt[i][0] = sqrt_gt_threshold(t.outer_cyl2.r);
     a->tiger_lt[i][0] = sqrt_lt_threshold(t.inner_cyl2.r);
     a->tiger_gt[i][1] = sqrt_gt_threshold(t.outer_cyl1.r);
@@ -2235,17 +1947,7 @@ int rt4_context_create(int device, uint32_t flags, rt4_context** out, char* err,
     if (e == hipSuccess) e = hipDeviceSynchronize();
   }
   if (e == hipSuccess && (flags & RT4_FLAG_SAMPLER_LUT)) {
-    // Diagnostic (round 6): RT4_WLUT_ALLOC=fine|uncached places the table in fine-grained or
-    // uncached device memory, to measure whether a 4-B gather then leaves L2 as a smaller fabric request. The
-    // default (coarse-grained hipMalloc) is what every product launch uses; images do not depend on it.
-    const char* wa = std::getenv("RT4_WLUT_ALLOC");
-    unsigned wflags = !wa ? hipDeviceMallocDefault
-                          : !std::strcmp(wa, "fine")     ? hipDeviceMallocFinegrained
-                          : !std::strcmp(wa, "uncached") ? hipDeviceMallocUncached
-                                                         : hipDeviceMallocDefault;
-    e = wflags == hipDeviceMallocDefault
-            ? hipMalloc(&c->d_wlut, (sizeof(WEntry) << 23) * RT4_ABL_WLUT_STRIDE)
-            : hipExtMallocWithFlags(reinterpret_cast<void**>(&c->d_wlut),(sizeof(WEntry) << 23) * RT4_ABL_WLUT_STRIDE, wflags);
+    e = hipMalloc(&c->d_wlut, sizeof(WEntry) << 23);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(rt4_build_wlut_kernel, dim3((1u << 23) / 256), dim3(256), 0, 0, c->d_wlut);
       e = hipGetLastError();
@@ -2533,7 +2235,7 @@ int launch_jobs(rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, i
   // Pipelined frames keep row-major order: the longest-first order only shortens the drain at the end
   // of a launch, which a pipelined launch pays once, and in the main phase row-major measured faster
   // (config 2 +1.5 %, config 3 +2 %; profiles/r02_ab.txt).
-  if ((!frames || RT4_LAST_FRAME_ORDER == 2) && !overlap) {
+  if (!frames && !overlap) {
   if (ctx->order_cap < tiles) {  // a frame larger than any before: grow once (allocates)
     HIP_TRY(hipStreamSynchronize(s));
     if (ctx->d_order) (void)hipFree(ctx->d_order);

@@ -6,7 +6,10 @@ The device code object is taken from the library's .hip_fatbin section (llvm-obj
 and disassembled (llvm-objdump). A loop is the address range of a backward branch: [target, branch]. A
 scratch instruction inside any such range of its kernel counts as "in a loop".
 
-Usage: python tools/codegen_check.py [--joins-only] [librt4.so | --object code.o]   (one line per trace kernel)
+Usage: python tools/codegen_check.py [--arch gfxNNN] [--joins-only] [librt4.so | --object code.o]
+(one line per trace kernel)
+  --arch       the offload target whose code object is taken from the library (default gfx950); the LLVM tools
+               come from $ROCM_LLVM_BIN (the csrc Makefile passes both, so an ARCH= or ROCM= build checks itself)
   --object     check a device code object (ELF) directly, e.g. llc's output for tools/codegen_repro/*.ll.gz
   --joins-only fail only on join-block copies (the stress builds may spill in their loops)
 Exit status 1 when a kernel fails a check: the csrc Makefile runs this after linking each library, so a build
@@ -35,15 +38,19 @@ def disassemble_object(co):
                           capture_output=True, text=True).stdout
 
 
-def disassemble(lib):
+def code_object(lib, d, arch="gfx950"):
+    """Writes the library's device code object for arch into the directory d; its path."""
+    fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
+    subprocess.run([f"{LLVM}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", lib, os.path.join(d, "x.so")],
+                   check=True, capture_output=True)
+    subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
+                    f"--targets=hipv4-amdgcn-amd-amdhsa--{arch}", f"--output={co}"], check=True, capture_output=True)
+    return co
+
+
+def disassemble(lib, arch="gfx950"):
     with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
-        subprocess.run([f"{LLVM}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", lib, os.path.join(d, "x.so")],
-                       check=True, capture_output=True)
-        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True, capture_output=True)
-        return subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co], check=True,
-                              capture_output=True, text=True).stdout
+        return disassemble_object(code_object(lib, d, arch))
 
 
 HEAD = re.compile(r"^[0-9a-f]+ <(\S+)>:$")
@@ -151,10 +158,10 @@ def short_name(sym):
     return f"K={m.group(1)} lut={m.group(2)} reuse={m.group(3)}"
 
 
-def report(lib=DEFAULT_LIB, obj=None):
+def report(lib=DEFAULT_LIB, obj=None, arch="gfx950"):
     """[(kernel, scratch accesses in loops, outside, join blocks with copies ahead of the EXEC restore)] for every
     trace kernel of lib (or of the device code object obj)."""
-    ks = kernels(disassemble_object(obj) if obj else disassemble(lib))
+    ks = kernels(disassemble_object(obj) if obj else disassemble(lib, arch))
     return [(short_name(k), *scratch_report(v), len(split_copies_before_join(v))) for k, v in sorted(ks.items())]
 
 
@@ -162,9 +169,14 @@ if __name__ == "__main__":
     argv = sys.argv[1:]
     joins_only = "--joins-only" in argv
     argv = [a for a in argv if a != "--joins-only"]
+    arch = "gfx950"
+    if "--arch" in argv:
+        at = argv.index("--arch")
+        arch = argv[at + 1]
+        del argv[at:at + 2]
     obj = argv[argv.index("--object") + 1] if "--object" in argv else None
     lib = argv[0] if argv and not obj else DEFAULT_LIB
-    rows = report(lib, obj)
+    rows = report(lib, obj, arch)
     if not rows:
         print(f"no trace kernels found in {obj or lib}")
         sys.exit(2)
