@@ -318,6 +318,14 @@ __device__ __forceinline__ unsigned rt4_lane_id() {
   return l;
 }
 
+// A wave-uniform value, said so to the compiler: it lives in a scalar register, and a branch on it is a scalar
+// branch instead of an EXEC-masked region (the refill's control)
+template <bool ON = true>
+__device__ __forceinline__ unsigned rt4_uni(unsigned v) {
+  if constexpr (ON) return __builtin_amdgcn_readfirstlane(v);
+  else return v;
+}
+
 struct RngState {
   uint32_t base;  // bits(scr.x) ^ (bits(scr.y) << 9) ^ uint_seed   (shader.frag:106-107)
   uint32_t iter;  // rand_iter_seed                                (shader.frag:92, :105)
@@ -645,6 +653,12 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
   constexpr unsigned CLAIM_TILES = static_cast<unsigned>(DEFER ? RT4_CLAIM_TILES_DEFER : RT4_CLAIM_TILES);
   uint32_t in_seed = useed;  // wave-uniform: the seed of the inbox's frame
   unsigned ring_n = 0;    // wave-uniform: outbox entries waiting to be written
+  // The refill's wave-uniform state (ring_n, spare, in_next, the claimed tile) goes through rt4_uni where it is
+  // read, so it lives in scalar registers and the refill's control is scalar branches. Not in
+  // the mirror-room tiger kernel with primary reuse: there the two-segment hand-out spills in the trace loop at
+  // the kernel's wave bound (profiles/r07_ab.txt), so it keeps the loop over the segments.
+  constexpr bool SUNI = !(REUSE && K != GENERIC && (K & K_TIGER) && ((K >> 8) & 0xFFu) >= 4);
+  auto uni = [](unsigned v) { return rt4_uni<SUNI>(v); };
   int s = 0, b = 0;
   uint32_t n_inter = 0, n_eval = 0;  // find_intersection calls of the reference / evaluated here (per lane, REUSE)
   // Without primary reuse every counted call is evaluated and a lane adds at most one per iteration: the wave
@@ -707,6 +721,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
     const unsigned long long pm = __ballot(pending);
     if (pm) {
       const unsigned np = static_cast<unsigned>(__popcll(pm));
+      ring_n = uni(ring_n);
       if (ring_n + np > 64u) flush_ring();
       if (pending) {
         const unsigned r = __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(pm >> 32),
@@ -721,6 +736,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
   // the queue is exhausted.
   auto claim_batch = [&]() -> bool {
     unsigned base = 0;
+    spare = uni(spare);
     if (CLAIM_TILES > 1 && (spare & (BATCH - 1u)) != 0u) {  // the next tile of the last claim: no atomic
       base = spare & ~(BATCH - 1u);
       spare += BATCH - 1u;  // the next position, one tile fewer
@@ -730,7 +746,8 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
       const unsigned nt =
           (CLAIM_TILES > 1 && a.n_frames > 1 && (spare & ~(BATCH - 1u)) + a.frame_tiles * BATCH < total) ? CLAIM_TILES
                                                                                                          : 1u;
-      if (lane == 0) base = atomicAdd(queue, BATCH * nt);
+      // one lane's atomic with a wave-uniform operand (no scan over the lanes around it)
+      if (lane == 0) base = atomicAdd(queue, uni(BATCH * nt));
       base = __builtin_amdgcn_readfirstlane(base);
       spare = (base + BATCH) | (nt - 1u);
     }
@@ -740,9 +757,9 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
     if (a.n_frames > 1) {
       frame = pos / a.frame_tiles;
       pos -= frame * a.frame_tiles;
-      in_seed = static_cast<uint32_t>(a.frame_seed[frame]);
+      in_seed = uni(static_cast<uint32_t>(a.frame_seed[frame]));
     }
-    const unsigned btile = order ? order[pos] : pos;
+    const unsigned btile = uni(order ? order[pos] : pos);
     const int job = (a.n_jobs > 1 && btile >= a.jobs[1].tile_base) + (a.n_jobs > 2 && btile >= a.jobs[2].tile_base);
     const JobArgs& J = a.jobs[job];
     const unsigned tile = btile - J.tile_base;
@@ -827,7 +844,8 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
     }
     if (!exhausted) {
       const unsigned long long idle = __ballot(!active);
-      bool refill = static_cast<unsigned>(__popcll(idle)) >= REFILL_K;
+      const unsigned nidle = uni(static_cast<unsigned>(__popcll(idle)));  // a 32-bit scalar compare below
+      bool refill = nidle >= REFILL_K;
       if (CLOCK && clock_on()) refill = refill && boundary;
       // phase-aligned: with active lanes left, wait (at most R + 1 iterations) for one of them to start
       // a sample; every active lane finishes a sample within R + 1 iterations, so the wait is bounded.
@@ -839,22 +857,12 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
         retire();
         const unsigned rank =
             __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(idle >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(idle), 0u));
-        const unsigned nidle = static_cast<unsigned>(__popcll(idle));
-        unsigned got = 0;
-        while (got < nidle) {
-          if (in_next == 64u) {
-            if (!claim_batch()) {
-              exhausted = true;
-#ifdef RT4_TAILSTATS
-              tail_exh = __builtin_amdgcn_s_memrealtime();
-#endif
-              break;
-            }
-            in_next = 0;
-          }
-          const unsigned n = min(nidle - got, 64u - in_next);
-          if (!active && rank >= got && rank < got + n) {
-            const unsigned e = wbase + in_next + (rank - got);
+        // The hand-out, wave-uniform control on the scalar unit: the inbox has 64 entries and nidle <= 64, so it is
+        // at most two straight-line segments, what is left of the inbox and, after one claim, the rest from the
+        // new one. Lanes ranked [g0, g0 + n) among the idle ones take the entries from e0 on.
+        auto hand_out = [&](unsigned g0, unsigned n, unsigned e0) {
+          if (!active && rank >= g0 && rank < g0 + n) {
+            const unsigned e = wbase + e0 + (rank - g0);
             // both reads before the test: one LDS round trip per hand-out instead of two
             const uint2 px = lds_in_px[e];
             const float4 d0 = lds_in_d0[e];
@@ -872,8 +880,43 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
               pending = !active;
             }
           }
-          in_next += n;
-          got += n;
+        };
+        if constexpr (SUNI) {
+          in_next = uni(in_next);
+          const unsigned n1 = min(nidle, 64u - in_next);
+          if (n1 != 0u) {
+            hand_out(0u, n1, in_next);
+            in_next += n1;
+          }
+          if (n1 < nidle) {  // the inbox is empty (in_next == 64)
+            if (claim_batch()) {
+              hand_out(n1, nidle - n1, 0u);
+              in_next = nidle - n1;
+            } else {
+              exhausted = true;
+#ifdef RT4_TAILSTATS
+              tail_exh = __builtin_amdgcn_s_memrealtime();
+#endif
+            }
+          }
+        } else {  // the same hand-out as a loop over the segments
+          unsigned got = 0;
+          while (got < nidle) {
+            if (in_next == 64u) {
+              if (!claim_batch()) {
+                exhausted = true;
+#ifdef RT4_TAILSTATS
+                tail_exh = __builtin_amdgcn_s_memrealtime();
+#endif
+                break;
+              }
+              in_next = 0;
+            }
+            const unsigned n = min(nidle - got, 64u - in_next);
+            hand_out(got, n, in_next);
+            in_next += n;
+            got += n;
+          }
         }
       }
     }
@@ -911,7 +954,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
       }
       if constexpr (TDEFER) {
         const unsigned long long tm = __ballot(need);
-        const bool run = tm != 0ull && (static_cast<unsigned>(__popcll(tm)) >= static_cast<unsigned>(RT4_DEFER_TIGER) ||
+        const bool run = tm != 0ull && (uni(static_cast<unsigned>(__popcll(tm))) >= static_cast<unsigned>(RT4_DEFER_TIGER) ||
                                         tdefer_age >= RT4_DEFER_TIGER_WAIT || tm == __ballot(active && !parked));
         if (tm != 0ull && !run) {
           ++tdefer_age;
@@ -992,7 +1035,7 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
       Cand inter = no_cand();
       if (active) inter = find_pre<K>(S, X, ray, pend);
       const unsigned long long pm = __ballot(pend != 0u);
-      const bool run = pm != 0ull && (static_cast<unsigned>(__popcll(pm)) >= static_cast<unsigned>(RT4_DEFER_EXACT) ||
+      const bool run = pm != 0ull && (uni(static_cast<unsigned>(__popcll(pm))) >= static_cast<unsigned>(RT4_DEFER_EXACT) ||
                                       defer_age >= RT4_DEFER_WAIT || pm == __ballot(active));
       if (pm != 0ull && !run) {
         parked = pend != 0u;

@@ -3,7 +3,10 @@
 hipcc -S listing (make -C 4d_ray_tracing_amd/csrc asm): VALU, and the scalar side split into exec-mask
 bookkeeping of divergent branches, branches, waits/nops, scalar memory and other SALU. The divergent regions
 (s_and_saveexec ... s_or_b64 exec) are listed by the VALU they guard, so small ones stand out.
-Usage: python tools/loop_mix.py <file.s> <kernel-substring>"""
+With a line range (the kernel's own line numbers, as the region list prints them) only that part of the loop is
+counted, and its VALU are split into the classes an attribution weighs by executed counts (fp32, int/bit, moves,
+selects, compares, lane reads/writes, the div/sqrt sequences' own instructions).
+Usage: python tools/loop_mix.py <file.s> <kernel-substring> [<first>:<last>]"""
 import collections
 import re
 import sys
@@ -35,8 +38,26 @@ def kind(op, line):
     return "other"
 
 
+def valu_class(op):
+    if op.startswith(("v_readlane", "v_writelane", "v_readfirstlane")):
+        return "lane read/write"
+    if op.startswith(("v_div_", "v_rcp", "v_sqrt", "v_rsq")):
+        return "div/sqrt seq"
+    if op.startswith("v_mov") or op.startswith("v_pk_mov"):
+        return "v_mov*"
+    if op.startswith("v_cndmask"):
+        return "v_cndmask"
+    if op.startswith("v_cmp"):
+        return "v_cmp*"
+    if re.search(r"_f(32|16|64)", op):
+        return "fp"
+    return "int/bit"
+
+
 def main():
     name, lines = kernel_body(sys.argv[1], sys.argv[2])
+    first, last = (int(x) for x in sys.argv[3].split(":")) if len(sys.argv) > 3 else (0, len(lines))
+    classes = collections.Counter()
     depth = 0
     mix = collections.Counter()
     regions = []  # (line, guarded VALU)
@@ -50,9 +71,11 @@ def main():
         if not t or t.startswith((";", ".")):
             continue
         op = t.split()[0]
-        if depth == 0:
+        if depth == 0 or not first <= i <= last:
             continue
         mix[kind(op, t)] += 1
+        if op.startswith("v_"):
+            classes[valu_class(op)] += 1
         m = re.search(r"s_and_saveexec_b64 (s\[\d+:\d+\])", t)
         if m:
             open_regions[m.group(1)] = [i, 0]
@@ -67,6 +90,8 @@ def main():
     print(f"trace-loop instructions (static): {total}")
     for k, n in mix.most_common():
         print(f"  {k:>12s} {n:5d}  {n / total * 100:5.1f} %")
+    if len(sys.argv) > 3:
+        print(f"VALU classes of lines {first}..{last}: " + ", ".join(f"{k} {n}" for k, n in classes.most_common()))
     small = [r for r in regions if r[1] <= 8]
     print(f"divergent regions (s_and_saveexec .. s_or_b64 exec) in the loop: {len(regions)}, "
           f"guarding <= 8 VALU: {len(small)}")
