@@ -748,6 +748,57 @@ int rt4_progressive_uniforms(const rt4_uniforms* base, uint32_t frame_number, rt
   return RT4_OK;
 }
 
+// ---- surface index: the order of the kernel's flat primitive table (rt4_trace.hip build_aux)
+int32_t rt4_scene_surface_count(const rt4_scene_desc* s) {
+  if (!s) return 0;
+  return s->n_spaces + s->n_spheres + s->n_cylinders + 2 * s->n_unions + 8 * s->n_hypercubes + 4 * s->n_tigers;
+}
+
+int rt4_scene_surface(const rt4_scene_desc* s, int32_t surface, int32_t* kind, int32_t* index, int32_t* part,
+                      rt4_material* material, char* err, size_t errlen) {
+  if (!s) return rt4_set_err(err, errlen, "NULL scene"), RT4_ERR_ARG;
+  if (s->n_spaces < 0 || s->n_spaces > RT4_MAX_SPACES || s->n_spheres < 0 || s->n_spheres > RT4_MAX_SPHERES ||
+      s->n_cylinders < 0 || s->n_cylinders > RT4_MAX_CYLINDERS || s->n_unions < 0 || s->n_unions > RT4_MAX_UNIONS ||
+      s->n_hypercubes < 0 || s->n_hypercubes > RT4_MAX_HYPERCUBES || s->n_tigers < 0 || s->n_tigers > RT4_MAX_TIGERS)
+    return rt4_set_err(err, errlen, "object count out of range"), RT4_ERR_ARG;
+  const int32_t count = rt4_scene_surface_count(s);
+  if (surface < 0 || surface >= count)
+    return rt4_set_err(err, errlen, "surface %d not in [0, %d)", surface, count), RT4_ERR_ARG;
+  int32_t k = surface, kd = 0, idx = 0, pt = 0;
+  const rt4_material* m = nullptr;
+  if (k < s->n_spaces) {
+    kd = RT4_GROUP_SPACES; idx = k; m = &s->spaces[idx].material;
+  } else if ((k -= s->n_spaces) < s->n_spheres) {
+    kd = RT4_GROUP_SPHERES; idx = k; m = &s->spheres[idx].material;
+  } else if ((k -= s->n_spheres) < s->n_cylinders) {
+    kd = RT4_GROUP_CYLINDERS; idx = k; m = &s->cylinders[idx].material;
+  } else if ((k -= s->n_cylinders) < 2 * s->n_unions) {
+    kd = RT4_GROUP_CYLINDERS_UNION; idx = k / 2; pt = k % 2;
+    m = pt == 0 ? &s->unions[idx].cylinder1.material : &s->unions[idx].cylinder2.material;
+  } else if ((k -= 2 * s->n_unions) < 8 * s->n_hypercubes) {
+    kd = RT4_GROUP_HYPERCUBE; idx = k / 8; pt = k % 8; m = &s->hypercubes[idx].cubes[pt].material;
+  } else {
+    k -= 8 * s->n_hypercubes;
+    kd = RT4_GROUP_TIGER; idx = k / 4; pt = k % 4;
+    const rt4_tiger& t = s->tigers[idx];
+    const rt4_cylinder* cs[4] = {&t.inner_cyl1, &t.outer_cyl1, &t.inner_cyl2, &t.outer_cyl2};
+    m = &cs[pt]->material;
+  }
+  if (kind) *kind = kd;
+  if (index) *index = idx;
+  if (part) *part = pt;
+  if (material) *material = *m;
+  return RT4_OK;
+}
+
+void rt4_denoise_params_default(rt4_denoise_params* p) {
+  if (!p) return;
+  p->levels = 3;
+  p->cos_min = 0.9f;
+  p->depth_tol = 0.1f;
+  p->max_refl_prob = 0.5f;
+}
+
 const char* rt4_build_info(void) {
   return "rt4 0.2 " RT4_KERNEL_VERSION " target=gfx950 fp32-contract=off div/sqrt=correctly-rounded built " __DATE__;
 }

@@ -20,6 +20,9 @@
 //                   [--raw]  (also the frame's bytes as stored, <prefix>_<section>.raw: bit-exact comparisons)
 //                   [--resume ckpt] [--checkpoint ckpt]  (one section: continue / save the progressive
 //                   accumulator, rt4_accum_load / rt4_accum_save; the reference has no counterpart)
+//                   [--denoise [levels]]  (next to every image also <name>_dn.<ext>: the final frame through the
+//                   edge-stopping filter, rt4_render_gbuffer_device of the last camera pose + rt4_denoise_device; the
+//                   accumulator itself is never filtered. One GPU only: not with --gpus)
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -297,6 +300,7 @@ int main(int argc, char** argv) {
   float move_seconds = 0.0f;
   std::string resume_path, checkpoint_path;
   bool png = false, rehearse = false, raw = false;
+  int denoise_levels = 0;  // --denoise: 0 = off
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -323,6 +327,13 @@ int main(int argc, char** argv) {
     else if (a == "--png") png = true;
     else if (a == "--raw") raw = true;
     else if (a == "--rehearse") rehearse = true;
+    else if (a == "--denoise") {
+      rt4_denoise_params dp;
+      rt4_denoise_params_default(&dp);
+      denoise_levels = dp.levels;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise_levels = std::atoi(argv[++i]);
+      if (denoise_levels < 1 || denoise_levels > RT4_DENOISE_MAX_LEVELS) die("--denoise", "levels must be 1..6");
+    }
     else die("unknown argument", a.c_str());
   }
   const int32_t format = fmt_name == "f16" ? RT4_FRAME_RGBA16F : fmt_name == "rgba8" ? RT4_FRAME_RGBA8 : RT4_FRAME_RGBA32F;
@@ -393,6 +404,7 @@ int main(int argc, char** argv) {
     cam.frame_number = static_cast<uint32_t>(frames_done + 1);
   }
 
+  if (gpus > 0 && denoise_levels > 0) die("--denoise", "not with --gpus: the frame is not filtered after the gather");
   if (gpus > 0) {  // pixel bands over GPUs 0..gpus-1, one RCCL gather (one section, resting camera)
     if (three || (keys && move_seconds > 0.0f)) die("--gpus", "needs one section and a resting camera");
     if (frames < 1 || band < 1) die("--gpus", "frames and band must be >= 1");
@@ -461,6 +473,8 @@ int main(int argc, char** argv) {
       us.push_back(u);
     }
   }
+  rt4_uniforms last_u[3];  // the last frame's uniforms of every section: the camera pose the images show
+  if (pipelined && !us.empty()) last_u[0] = us.back();
   HIP_CHECK(hipEventRecord(e0, nullptr));
   if (pipelined) {
     const rt4_region reg{0, 0, cw[0], ch[0], 0, 0};
@@ -477,6 +491,7 @@ int main(int argc, char** argv) {
       jobs[q].region = rt4_region{0, 0, cw[q], ch[q], 0, 0};
       jobs[q].d_frame = d_frame[q];
       jobs[q].row_stride_px = cw[q];
+      last_u[q] = jobs[q].u;
     }
     RT4_CHECK(rt4_render_sections_device(ctx, jobs, n_img, format, d_count, nullptr, err, sizeof err));
     if (keys && move_seconds > 0.0f) rt4_camera_move(&cam, keys, move_seconds);  // move(seconds), main.cpp:95-96
@@ -496,6 +511,31 @@ int main(int argc, char** argv) {
     RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(path.c_str(), host.data(), format, cw[q], ch[q], cw[q], err, sizeof err));
     if (raw) write_raw(out + "_" + names[q] + ".raw", host);
     std::printf("wrote %s (%d x %d)\n", path.c_str(), cw[q], ch[q]);
+    if (denoise_levels > 0 && frames >= 1) {
+      // the picture to look at: the final frame filtered along the primary hits of its camera pose (one G-buffer
+      // per pose and section); d_frame stays the accumulator
+      const size_t npx = static_cast<size_t>(cw[q]) * ch[q];
+      rt4_gbuffer_px* d_gbuf = nullptr;
+      void* d_dn = nullptr;
+      HIP_CHECK(hipMalloc(&d_gbuf, npx * sizeof(rt4_gbuffer_px)));
+      HIP_CHECK(hipMalloc(&d_dn, npx * px));
+      const rt4_region reg{0, 0, cw[q], ch[q], 0, 0};
+      rt4_denoise_params dp;
+      rt4_denoise_params_default(&dp);
+      dp.levels = denoise_levels;
+      RT4_CHECK(rt4_render_gbuffer_device(ctx, &last_u[q], &reg, d_gbuf, cw[q], nullptr, err, sizeof err));
+      RT4_CHECK(rt4_denoise_device(ctx, d_frame[q], cw[q], d_dn, cw[q], format, cw[q], ch[q], d_gbuf, cw[q], &dp, nullptr, err,
+                                   sizeof err));
+      HIP_CHECK(hipDeviceSynchronize());
+      std::vector<unsigned char> dn(host.size());
+      HIP_CHECK(hipMemcpy(dn.data(), d_dn, dn.size(), hipMemcpyDeviceToHost));
+      const std::string dn_path = out + "_" + names[q] + "_dn" + (png ? ".png" : ".ppm");
+      RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(dn_path.c_str(), dn.data(), format, cw[q], ch[q], cw[q], err, sizeof err));
+      if (raw) write_raw(out + "_" + names[q] + "_dn.raw", dn);
+      std::printf("wrote %s (%d x %d, %d filter levels)\n", dn_path.c_str(), cw[q], ch[q], denoise_levels);
+      (void)hipFree(d_gbuf);
+      (void)hipFree(d_dn);
+    }
     if (q == 0 && !checkpoint_path.empty()) {
       // frames_done counts camera-resting frames only: a moving camera restarts the blend (frame_number 1)
       RT4_CHECK(rt4_accum_save_key(checkpoint_path.c_str(), host.data(), format, cw[0], ch[0], cw[0],

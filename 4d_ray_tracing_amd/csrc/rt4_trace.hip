@@ -1357,6 +1357,82 @@ __global__ void rt4_tile_order_kernel(const rt4_scene_desc* __restrict__ S, cons
   order[pos] = t;
 }
 
+// ---------------------------------------------------------------- primary-hit G-buffer (rt4.h rt4_gbuffer_px)
+// Finder<GENERIC> names a hit by the byte offset of its material inside rt4_scene_desc (Hit.mat); the surface index
+// of rt4.h is the position in the flat primitive table (build_aux), which is what the specialised kernels' Hit.mat
+// holds. The offset decides the array and the element; the counts of the arrays before it give the base.
+__device__ __forceinline__ int surface_of_offset(const rt4_scene_desc* __restrict__ S, int off) {
+  const int o = off;
+  if (o < static_cast<int>(offsetof(rt4_scene_desc, n_spheres)))
+    return (o - static_cast<int>(offsetof(rt4_scene_desc, spaces))) / static_cast<int>(sizeof(rt4_space));
+  int base = S->n_spaces;
+  if (o < static_cast<int>(offsetof(rt4_scene_desc, n_cylinders)))
+    return base + (o - static_cast<int>(offsetof(rt4_scene_desc, spheres))) / static_cast<int>(sizeof(rt4_sphere));
+  base += S->n_spheres;
+  if (o < static_cast<int>(offsetof(rt4_scene_desc, n_unions)))
+    return base + (o - static_cast<int>(offsetof(rt4_scene_desc, cylinders))) / static_cast<int>(sizeof(rt4_cylinder));
+  base += S->n_cylinders;
+  // composites are arrays of cylinders / cubes: the element's position inside the whole array is the part number
+  if (o < static_cast<int>(offsetof(rt4_scene_desc, n_hypercubes)))
+    return base + (o - static_cast<int>(offsetof(rt4_scene_desc, unions))) / static_cast<int>(sizeof(rt4_cylinder));
+  base += 2 * S->n_unions;
+  if (o < static_cast<int>(offsetof(rt4_scene_desc, n_tigers)))
+    return base + (o - static_cast<int>(offsetof(rt4_scene_desc, hypercubes))) / static_cast<int>(sizeof(rt4_cube));
+  base += 8 * S->n_hypercubes;
+  return base + (o - static_cast<int>(offsetof(rt4_scene_desc, tigers))) / static_cast<int>(sizeof(rt4_cylinder));
+}
+static_assert(sizeof(rt4_cylinders_union) == 2 * sizeof(rt4_cylinder) && sizeof(rt4_hypercube) == 8 * sizeof(rt4_cube) &&
+                  sizeof(rt4_tiger) == 4 * sizeof(rt4_cylinder),
+              "composites are plain arrays of their parts (surface_of_offset)");
+static_assert(sizeof(rt4_gbuffer_px) == 32, "rt4_gbuffer_px is two 16-B words");
+
+struct GbufArgs {
+  JobArgs J;  // the image: resolution, matrix, camera basis, region, row stride (frame unused)
+  float focus[4];
+  unsigned tiles;  // 8x8 tiles of the region
+};
+
+// One lane per pixel, one wave per 8x8 tile (the trace kernel's pixel mapping): the primary ray exactly as the trace
+// kernel's refill builds it, then find / resolve / material of the scene's kernel shape, and one 32-B record.
+template <uint32_t K>
+__global__ __launch_bounds__(256) void rt4_gbuffer_kernel(const rt4_scene_desc* __restrict__ S,
+                                                          const SceneAux* __restrict__ X, const GbufArgs g,
+                                                          rt4_gbuffer_px* __restrict__ out) {
+#ifdef RT4_LANESTATS
+  rt4_ls_counter = nullptr;  // diagnostic build: only the trace kernel counts
+#endif
+  const unsigned tile = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (tile >= g.tiles) return;
+  const JobArgs& J = g.J;
+  const int jj = static_cast<int>((tile % J.tiles_x) * 8u + (lane & 7u));
+  const int ii = static_cast<int>((tile / J.tiles_x) * 8u + (lane >> 3));
+  if (jj >= J.reg.w || ii >= J.reg.h) return;
+  // main(): scr_coord = gl_FragCoord.xy / resolution (shader.frag:515-516)
+  const float sx = (static_cast<float>(J.reg.x0 + jj) + 0.5f) / J.resolution[0];
+  const float sy = (static_cast<float>(region_row(J.reg, ii)) + 0.5f) / J.resolution[1];
+  // ray_drct(), shader.frag:501-505
+  const float mx = (sx - 0.5f) * J.mtr_sizes[0];
+  const float my = (0.5f - sy) * J.mtr_sizes[1];
+  V4 dd = mad(ld4(J.right_drct), mx, mad(ld4(J.top_drct), my, ld4(J.vec_to_mtr)));
+  dd = divs(dd, length(dd));
+  const Ray ray{ld4(g.focus), dd};
+  const typename Finder<K>::R c = Finder<K>::find(S, X, X->prims, ray);
+  float4 n = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float depth = __builtin_inff(), refl = 0.0f, glow = 0.0f;
+  int surface = -1;
+  if (c.hit) {
+    const Hit h = Finder<K>::resolve(X->prims, ray, c);
+    V3 col;
+    Finder<K>::material(S, X->prims, h, glow, refl, col);
+    n = make_float4(h.norm.x, h.norm.y, h.norm.z, h.norm.w);
+    depth = c.dist;
+    surface = K == GENERIC ? surface_of_offset(S, h.mat) : h.mat;
+  }
+  float4* o = reinterpret_cast<float4*>(out + static_cast<int64_t>(ii) * J.row_stride_px + jj);
+  o[0] = n;
+  o[1] = make_float4(depth, __int_as_float(surface), refl, glow);
+}
+
 // The frames of a pipelined launch blended in order into the frame buffer (rt4_render_frames_device):
 // per pixel the same blend as write_pixel, frame after frame, each rounded to the frame format.
 // count_src (an overlapped single frame): the trace kernel's count, moved into the caller's counter here, on
@@ -1419,19 +1495,21 @@ typedef void (*TraceFn)(const rt4_scene_desc*, const SceneAux*, const KernelArgs
                         const WEntry*, unsigned*, unsigned*);
 typedef void (*FindFn)(const rt4_scene_desc*, const SceneAux*, const float*, float*, float*, int64_t);
 typedef void (*OrderFn)(const rt4_scene_desc*, const SceneAux*, const KernelArgs, unsigned*, unsigned*);
+typedef void (*GbufFn)(const rt4_scene_desc*, const SceneAux*, const GbufArgs, rt4_gbuffer_px*);
 
 struct Variant {
   uint32_t shape;
   TraceFn trace[2][2];  // [lut][primary reuse]
   FindFn find;
   OrderFn order;
+  GbufFn gbuffer;
 };
 
 #define RT4_VARIANT(K)                                                                                  \
   {K,                                                                                                   \
    {{rt4_trace_kernel<K, false, false>, rt4_trace_kernel<K, false, (K) != GENERIC>},                    \
     {rt4_trace_kernel<K, true, false>, rt4_trace_kernel<K, true, (K) != GENERIC>}},                     \
-   rt4_find_kernel<K>, rt4_tile_order_kernel<K>}
+   rt4_find_kernel<K>, rt4_tile_order_kernel<K>, rt4_gbuffer_kernel<K>}
 // shape | (n_spaces+1) << 8 | (n_spheres+1) << 16 | (n_cylinders+1) << 24 (rt4_fast.h sh_count),
 // from the scene's object counts (the same encoding scene_shape() computes)
 #define SH(K, nsp, nsh, ncy) \
@@ -1565,6 +1643,10 @@ struct rt4_context {
   size_t ofcolor_cap[RT4_OVERLAP_SLOTS] = {};  // bytes of each slot buffer (grown to the largest launch it served)
   bool overlapped = false, last_deep = false;  // the last overlapped launch's rotation
   unsigned long long* d_ocount = nullptr;  // one counter per slot
+  // Scratch of rt4_denoise_device (rt4_denoise.h): two fp32 RGBA images for the levels and the repacked guide
+  // (normal 16 B, {id, depth} 8 B), 56 B per pixel of the largest frame filtered, in one allocation.
+  void* d_denoise = nullptr;
+  size_t denoise_px = 0;  // pixels it holds
 };
 
 #define HIP_TRY(expr)                                                                            \
@@ -2028,6 +2110,7 @@ void rt4_context_destroy(rt4_context* ctx) {
   if (ctx->d_ocount) (void)hipFree(ctx->d_ocount);
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
   if (ctx->d_eval) (void)hipFree(ctx->d_eval);
+  if (ctx->d_denoise) (void)hipFree(ctx->d_denoise);
   delete ctx;
 }
 
@@ -2705,3 +2788,104 @@ int rt4_debug_find_intersection(rt4_context* ctx, const float* rays, float* out,
 }
 
 }  // extern "C"
+
+// ==================================================================================== G-buffer, denoiser
+namespace {
+
+// A launch of the context on stream s that is not a render (G-buffer, denoise): ordered behind the context's previous
+// launch when that ran on another stream. done_launch() afterwards: rt4_context_set_scene and the next launch on
+// another stream wait for it.
+int order_launch(rt4_context* ctx, hipStream_t s, char* err, size_t errlen) {
+  if (ctx->launched && s != ctx->last_stream) HIP_TRY(hipStreamWaitEvent(s, ctx->done, 0));
+  return RT4_OK;
+}
+int done_launch(rt4_context* ctx, hipStream_t s, char* err, size_t errlen) {
+  const hipError_t re = hipEventRecord(ctx->done, s);
+  ctx->last_stream = s;
+  ctx->launched = true;
+  if (re != hipSuccess) {
+    rt4_set_err(err, errlen, "hipEventRecord failed: %s", hipGetErrorString(re));
+    return RT4_ERR_HIP;
+  }
+  return RT4_OK;
+}
+
+// Elements of a strided w x h image: the last row ends at its w-th pixel.
+size_t image_span(int64_t stride_px, int32_t w, int32_t h) {
+  return static_cast<size_t>(h - 1) * static_cast<size_t>(stride_px) + static_cast<size_t>(w);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt4_render_gbuffer_device(rt4_context* ctx, const rt4_uniforms* u, const rt4_region* region, rt4_gbuffer_px* d_gbuf,
+                              int64_t row_stride_px, void* stream, char* err, size_t errlen) {
+  if (!ctx || !u || !region || !d_gbuf) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
+  if (!ctx->has_scene) return rt4_set_err(err, errlen, "context has no scene (rt4_context_set_scene)"), RT4_ERR_ARG;
+  rt4_uniforms uc = *u;  // samples and reflections_amount are not used: any value passes the shared check
+  uc.samples = 0;
+  uc.reflections_amount = 0;
+  const int st = rt4_check_render_args(&uc, region, row_stride_px, err, errlen);
+  if (st != RT4_OK) return st;
+  if (reinterpret_cast<uintptr_t>(d_gbuf) % 16u != 0)
+    return rt4_set_err(err, errlen, "G-buffer not 16-byte aligned"), RT4_ERR_ARG;
+  if (region->w == 0 || region->h == 0) return RT4_OK;
+  GbufArgs g;
+  std::memset(&g, 0, sizeof g);
+  JobArgs& J = g.J;
+  std::memcpy(J.resolution, u->resolution, sizeof J.resolution);
+  std::memcpy(J.mtr_sizes, u->mtr_sizes, sizeof J.mtr_sizes);
+  std::memcpy(J.vec_to_mtr, u->vec_to_mtr, sizeof J.vec_to_mtr);
+  std::memcpy(J.top_drct, u->top_drct, sizeof J.top_drct);
+  std::memcpy(J.right_drct, u->right_drct, sizeof J.right_drct);
+  std::memcpy(g.focus, u->focus, sizeof g.focus);
+  J.reg = *region;
+  J.row_stride_px = row_stride_px;
+  J.tiles_x = static_cast<unsigned>((region->w + 7) / 8);
+  g.tiles = J.tiles_x * static_cast<unsigned>((region->h + 7) / 8);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int rc = order_launch(ctx, s, err, errlen);
+  if (rc != RT4_OK) return rc;
+  (void)hipGetLastError();  // a sticky error of an earlier, unrelated call must not be taken for this launch's
+  hipLaunchKernelGGL(variant_for(ctx->shape).gbuffer, dim3((g.tiles + 3u) / 4u), dim3(256), 0, s, ctx->d_scene,
+                     scene_aux(ctx), g, d_gbuf);
+  const hipError_t le = hipGetLastError();
+  rc = done_launch(ctx, s, err, errlen);
+  if (le != hipSuccess) {
+    rt4_set_err(err, errlen, "G-buffer kernel launch failed: %s", hipGetErrorString(le));
+    return RT4_ERR_HIP;
+  }
+  return rc;
+}
+
+int rt4_render_gbuffer_host(rt4_context* ctx, const rt4_uniforms* u, const rt4_region* region, rt4_gbuffer_px* gbuf,
+                            int64_t row_stride_px, char* err, size_t errlen) {
+  if (!ctx || !u || !region || !gbuf) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
+  if (region->w < 0 || region->h < 0 || (region->w > 0 && row_stride_px < region->w))
+    return rt4_set_err(err, errlen, "bad region or row stride"), RT4_ERR_ARG;
+  if (region->w == 0 || region->h == 0) return RT4_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t bytes = image_span(row_stride_px, region->w, region->h) * sizeof(rt4_gbuffer_px);
+  void* d = nullptr;
+  HIP_TRY(hipMalloc(&d, bytes));
+  hipError_t e = hipMemcpy(d, gbuf, bytes, hipMemcpyHostToDevice);  // the padding between rows keeps its bytes
+  int st = RT4_OK;
+  if (e == hipSuccess) {
+    st = rt4_render_gbuffer_device(ctx, u, region, static_cast<rt4_gbuffer_px*>(d), row_stride_px, nullptr, err, errlen);
+    if (st == RT4_OK) {
+      e = hipDeviceSynchronize();
+      if (e == hipSuccess) e = hipMemcpy(gbuf, d, bytes, hipMemcpyDeviceToHost);
+    }
+  }
+  (void)hipFree(d);
+  if (st == RT4_OK && e != hipSuccess) {
+    rt4_set_err(err, errlen, "render_gbuffer_host failed: %s", hipGetErrorString(e));
+    st = RT4_ERR_HIP;
+  }
+  return st;
+}
+
+}  // extern "C"
+
+#include "rt4_denoise.h"

@@ -143,6 +143,27 @@ class SectionJob(Structure):  # rt4.h rt4_section_job
     _fields_ = [("u", Uniforms), ("region", Region), ("d_frame", c_void_p), ("row_stride_px", c_int64)]
 
 
+class GBufferPx(Structure):  # rt4.h rt4_gbuffer_px: the primary hit of one pixel
+    _fields_ = [("normal", F4), ("depth", c_float), ("surface", c_int32), ("refl_prob", c_float), ("glow", c_float)]
+
+
+class DenoiseParams(Structure):  # rt4.h rt4_denoise_params
+    _fields_ = [("levels", c_int32), ("cos_min", c_float), ("depth_tol", c_float), ("max_refl_prob", c_float)]
+
+
+DENOISE_MAX_LEVELS = 6
+
+
+def _gbuffer_dtype():
+    import numpy as np
+
+    return np.dtype([("normal", "<f4", (4,)), ("depth", "<f4"), ("surface", "<i4"), ("refl_prob", "<f4"), ("glow", "<f4")])
+
+
+# numpy layout of rt4_gbuffer_px (32 B): arrays of shape (h, stride) for Tracer.render_gbuffer_host / denoise_host
+GBUFFER_DTYPE = _gbuffer_dtype()
+
+
 def _load(path=None):
     path = path or LIB_PATH
     if not os.path.exists(path):
@@ -217,6 +238,17 @@ def _load(path=None):
                                c_int),
         "rt4_accum_key": ([c_void_p, c_void_p], c_uint32),
         "rt4_accum_key_of": ([c_char_p, POINTER(c_uint32)] + E, c_int),
+        "rt4_scene_surface_count": ([POINTER(SceneDesc)], c_int32),
+        "rt4_scene_surface": ([POINTER(SceneDesc), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                               POINTER(Material)] + E, c_int),
+        "rt4_render_gbuffer_device": ([c_void_p, POINTER(Uniforms), POINTER(Region), c_void_p, c_int64, c_void_p] + E, c_int),
+        "rt4_render_gbuffer_host": ([c_void_p, POINTER(Uniforms), POINTER(Region), c_void_p, c_int64] + E, c_int),
+        "rt4_denoise_params_default": ([POINTER(DenoiseParams)], None),
+        "rt4_denoise_device": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64,
+                                POINTER(DenoiseParams), c_void_p] + E, c_int),
+        "rt4_denoise_host": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64,
+                              POINTER(DenoiseParams)] + E, c_int),
+        "rt4_context_denoise_bytes": ([c_void_p], c_uint64),
     }
     tolerant = os.environ.get("RT4_AB_TOLERANT") == "1"  # tools/abtest.sh: older builds lack newer exports
     for name, (argtypes, restype) in sig.items():
@@ -246,7 +278,9 @@ EXPORTED = (
     "rt4_camera_frame_uniforms rt4_write_ppm rt4_frame_format_bytes rt4_render_device_ex rt4_render_host_ex rt4_progressive_uniforms rt4_render_sections_device "
     "rt4_debug_verify_div rt4_debug_sky_threshold rt4_context_evaluated rt4_render_frames_device rt4_context_reserve_frames rt4_context_frames_per_launch "
     "rt4_band_plan rt4_bands_unpermute_device rt4_context_frame_scratch_bytes rt4_context_overlap_bytes rt4_context_reserve_overlap rt4_accum_save rt4_accum_info rt4_accum_load rt4_write_png "
-    "rt4_accum_save_key rt4_accum_key rt4_accum_key_of"
+    "rt4_accum_save_key rt4_accum_key rt4_accum_key_of "
+    "rt4_scene_surface_count rt4_scene_surface rt4_render_gbuffer_device rt4_render_gbuffer_host "
+    "rt4_denoise_params_default rt4_denoise_device rt4_denoise_host rt4_context_denoise_bytes"
 ).split()
 
 if ctypes.sizeof(SceneDesc) != lib.rt4_scene_desc_size() or ctypes.sizeof(Uniforms) != lib.rt4_uniforms_size():
@@ -417,6 +451,30 @@ class Scene:
 
     def groups(self):
         return [(g.kind, g.first, g.count, g.outer, g.new_first) for g in self.desc.groups[: self.desc.n_groups]]
+
+    def surface_count(self) -> int:
+        """Surfaces of the scene: everything a G-buffer pixel can name (rt4_scene_surface_count)."""
+        return int(lib.rt4_scene_surface_count(byref(self.desc)))
+
+    def surface(self, i: int) -> dict:
+        """Surface i (rt4_scene_surface): kind (GROUP_*), index in the kind's array, part inside a composite and
+        the material (glow, refl_prob, color)."""
+        kind, index, part, m = c_int32(), c_int32(), c_int32(), Material()
+        err = _errbuf()
+        _check(lib.rt4_scene_surface(byref(self.desc), i, byref(kind), byref(index), byref(part), byref(m), err, len(err)), err)
+        return {"kind": kind.value, "index": index.value, "part": part.value, "glow": m.glow, "refl_prob": m.refl_prob,
+                "color": tuple(m.color)}
+
+
+def denoise_params(levels: int | None = None, cos_min: float | None = None, depth_tol: float | None = None,
+                   max_refl_prob: float | None = None) -> DenoiseParams:
+    """rt4_denoise_params_default (3 levels, 0.9, 0.1, 0.5) with the given fields replaced."""
+    p = DenoiseParams()
+    lib.rt4_denoise_params_default(byref(p))
+    for name, v in (("levels", levels), ("cos_min", cos_min), ("depth_tol", depth_tol), ("max_refl_prob", max_refl_prob)):
+        if v is not None:
+            setattr(p, name, v)
+    return p
 
 
 def region(w: int, h: int, x0: int = 0, y0: int = 0, band_rows: int = 0, band_step: int = 0) -> Region:
@@ -592,6 +650,7 @@ class Tracer:
     def set_scene(self, scene: Scene) -> None:
         err = _errbuf()
         _check(self._lib.rt4_context_set_scene(self._h, byref(scene.desc), err, len(err)), err)
+        self._scene = scene  # pick() names the object under the cursor with it
 
     def render_device(self, u: Uniforms, reg: Region, frame_ptr: int, row_stride_px: int, counter_ptr: int = 0,
                       stream: int = 0) -> None:
@@ -673,6 +732,71 @@ class Tracer:
         _check(self._lib.rt4_render_host(self._h, byref(u), byref(reg), c_void_p(frame.ctypes.data), stride, byref(n), err,
                                    len(err)), err)
         return n.value
+
+    def render_gbuffer_device(self, u: Uniforms, reg: Region, gbuf_ptr: int, row_stride_px: int, stream: int = 0) -> None:
+        """Asynchronous: the primary hit of every pixel of `reg` into a device array of rt4_gbuffer_px (32 B each)."""
+        err = _errbuf()
+        _check(self._lib.rt4_render_gbuffer_device(self._h, byref(u), byref(reg), c_void_p(gbuf_ptr), row_stride_px,
+                                                   c_void_p(stream or None), err, len(err)), err)
+
+    def render_gbuffer_host(self, u: Uniforms, reg: Region, gbuf=None, row_stride_px: int | None = None):
+        """Synchronous: the G-buffer of `reg` into a host array (h, stride) of GBUFFER_DTYPE (a new one if None)."""
+        import numpy as np
+
+        if gbuf is None:
+            gbuf = np.zeros((reg.h, row_stride_px or reg.w), GBUFFER_DTYPE)
+        assert gbuf.dtype == GBUFFER_DTYPE and gbuf.flags["C_CONTIGUOUS"]
+        stride = row_stride_px if row_stride_px is not None else gbuf.shape[1]
+        err = _errbuf()
+        _check(self._lib.rt4_render_gbuffer_host(self._h, byref(u), byref(reg), c_void_p(gbuf.ctypes.data), stride, err,
+                                                 len(err)), err)
+        return gbuf
+
+    def pick(self, u: Uniforms, x: int, y: int) -> dict:
+        """What is under the cursor at pixel (x, y) of the image of `u` (row 0 on top): the pixel's G-buffer record
+        under "px" (a GBUFFER_DTYPE scalar: normal, depth, surface, refl_prob, glow), "hit", and under "object"
+        rt4_scene_surface's answer for the surface hit (None on a miss)."""
+        px = self.render_gbuffer_host(u, region(1, 1, x, y))[0, 0]
+        hit = bool(px["surface"] >= 0)
+        scene = getattr(self, "_scene", None)
+        return {"px": px, "hit": hit, "object": scene.surface(int(px["surface"])) if hit and scene is not None else None}
+
+    def denoise_device(self, in_ptr: int, in_stride_px: int, out_ptr: int, out_stride_px: int, fmt: int, w: int, h: int,
+                       gbuf_ptr: int, gbuf_stride_px: int, params: DenoiseParams | None = None, stream: int = 0) -> None:
+        """Asynchronous edge-stopping filter of a device frame into another one (rt4_denoise_device). For display:
+        keep accumulating into the input frame, never into the filtered one."""
+        p = params if params is not None else denoise_params()
+        err = _errbuf()
+        _check(self._lib.rt4_denoise_device(self._h, c_void_p(in_ptr or None), in_stride_px, c_void_p(out_ptr or None),
+                                            out_stride_px, fmt, w, h, c_void_p(gbuf_ptr or None), gbuf_stride_px, byref(p),
+                                            c_void_p(stream or None), err, len(err)), err)
+
+    def denoise_host(self, frame, gbuf, params: DenoiseParams | None = None, out=None, fmt: int | None = None,
+                     w: int | None = None):
+        """Synchronous filter of a host frame (h, stride, 4) guided by a host G-buffer (h, stride) of GBUFFER_DTYPE;
+        w: the image width when the rows are padded (default: every column). Returns `out` (a new array if None)."""
+        import numpy as np
+
+        if fmt is None:
+            fmt = {np.dtype("float32"): FRAME_RGBA32F, np.dtype("float16"): FRAME_RGBA16F,
+                   np.dtype("uint8"): FRAME_RGBA8}[frame.dtype]
+        assert frame.dtype == np.dtype(FRAME_NUMPY[fmt]) and frame.flags["C_CONTIGUOUS"]
+        assert gbuf.dtype == GBUFFER_DTYPE and gbuf.flags["C_CONTIGUOUS"]
+        h = frame.shape[0]
+        w = frame.shape[1] if w is None else w
+        if out is None:
+            out = np.zeros((h, w, 4), frame.dtype)
+        assert out.dtype == frame.dtype and out.flags["C_CONTIGUOUS"]
+        p = params if params is not None else denoise_params()
+        err = _errbuf()
+        _check(self._lib.rt4_denoise_host(self._h, c_void_p(frame.ctypes.data), frame.shape[1], c_void_p(out.ctypes.data),
+                                          out.shape[1], fmt, w, h, c_void_p(gbuf.ctypes.data), gbuf.shape[1], byref(p), err,
+                                          len(err)), err)
+        return out
+
+    def denoise_bytes(self) -> int:
+        """Bytes of the context's denoise scratch (rt4.h rt4_context_denoise_bytes)."""
+        return int(self._lib.rt4_context_denoise_bytes(self._h))
 
     @property
     def kernel_shape(self) -> int:

@@ -317,6 +317,17 @@ int rt4_scene_validate(const rt4_scene_desc* s, char* err, size_t errlen);
  * the shipped shader.frag default), "cylinder4d" (Четырёхмерный цилиндр), "hypercube" (Гиперкуб). */
 int rt4_scene_builtin(const char* name, rt4_scene_desc* out, char* err, size_t errlen);
 
+/* ---- surface index ---------------------------------------------------------
+ * A flat numbering of everything a ray can hit, in the order of the arrays of rt4_scene_desc, whether or
+ * not a group tests the object: spaces[i], spheres[i], cylinders[i], each unions[i] as cylinder1, cylinder2,
+ * each hypercubes[i] as cubes[0..7], each tigers[i] as inner_cyl1, outer_cyl1, inner_cyl2, outer_cyl2.
+ * rt4_gbuffer_px.surface holds this number. */
+int32_t rt4_scene_surface_count(const rt4_scene_desc* s);
+/* kind: rt4_group_kind of the owner; index: object in its kind's array; part: 0, or 0..1 / 0..7 / 0..3 inside a
+ * union / hypercube / tiger. Any out pointer may be NULL. RT4_ERR_ARG for surface outside [0, count). */
+int rt4_scene_surface(const rt4_scene_desc* s, int32_t surface, int32_t* kind, int32_t* index, int32_t* part,
+                      rt4_material* material, char* err, size_t errlen);
+
 /* ---- device context + trace kernel --------------------------------------------------------- */
 typedef struct rt4_context rt4_context;
 
@@ -482,6 +493,64 @@ int rt4_band_plan(int32_t width, int32_t height, int32_t world, int32_t band, in
  * hipStream_t of the device that holds both buffers). */
 int rt4_bands_unpermute_device(const void* d_gathered, void* d_image, int32_t width, int32_t height, int32_t world,
                                int32_t band, int32_t rows_max, int32_t format, void* stream, char* err, size_t errlen);
+
+/* ---- primary-hit G-buffer, picking (no reference counterpart) ----------------
+ * Every sample of a pixel starts with the same primary ray (shader.frag:519-521, no jitter), so the primary hit
+ * is a noise-free function of the camera: one find_intersection per pixel gives it exactly. */
+typedef struct rt4_gbuffer_px { /* 32 B */
+  float normal[4];  /* the hit's normal exactly as find_intersection returns it; 0,0,0,0 on a miss */
+  float depth;      /* the hit's dist (bits as returned, +inf and NaN hits included); +inf on a miss */
+  int32_t surface;  /* surface index (rt4_scene_surface); -1 on a miss */
+  float refl_prob;  /* the hit material's; 0 on a miss */
+  float glow;       /* the hit material's; 0 on a miss */
+} rt4_gbuffer_px;
+
+/* The primary hit of every pixel of `region` with the context's scene: pixel (i, j) of the region at
+ * d_gbuf + i*row_stride_px + j. One lane per pixel runs the trace kernel's primary-ray arithmetic and the
+ * find_intersection of the context's selected kernel. Uses u's resolution, mtr_sizes, focus, vec_to_mtr, top_drct
+ * and right_drct; ignores seed, samples, part and reflections_amount. Asynchronous on `stream`, no allocation, no
+ * random numbers, nothing added to any intersection counter. Ordered with the context's other launches
+ * (rt4_context_set_scene waits for it). d_gbuf must be 16-byte aligned (RT4_ERR_ARG otherwise). A pick is the
+ * 1 x 1 region at the cursor. */
+int rt4_render_gbuffer_device(rt4_context* ctx, const rt4_uniforms* u, const rt4_region* region, rt4_gbuffer_px* d_gbuf,
+                              int64_t row_stride_px, void* stream, char* err, size_t errlen);
+/* The same into a host buffer (synchronous; pixels outside the region keep their bytes). */
+int rt4_render_gbuffer_host(rt4_context* ctx, const rt4_uniforms* u, const rt4_region* region, rt4_gbuffer_px* gbuf,
+                            int64_t row_stride_px, char* err, size_t errlen);
+
+/* ---- edge-stopping a-trous filter guided by the G-buffer ---------------------
+ * For display only: the caller keeps its accumulator (the frame the renders blend into) and never passes the
+ * filtered image back as old_frame. The frame and the G-buffer share the pixel indexing [0,w) x [0,h).
+ * Definition (fp32 round-to-nearest, no contraction; the kernel matches it bit for bit):
+ *   C_0 = the decoded input (float as stored, half -> float, u / 255.0f). p is filterable iff
+ *   surface(p) >= 0 && refl_prob(p) <= max_refl_prob. For level l = 0 .. levels-1, s = 2^l, H = {1/16,1/4,3/8,1/4,1/16}:
+ *   a pixel that is not filterable keeps C_l(p); a filterable p sums the taps dy = -2..2 (outer), dx = -2..2 (inner),
+ *   q = p + s*(dx, dy); a tap counts iff q is inside the image and (q == p, or q is filterable, surface(q) ==
+ *   surface(p), dot(n_p, n_q) >= cos_min (the fma chain of DESIGN.md §3) and fabsf(z_q - z_p) <= depth_tol * z_p);
+ *   with k = H[dy+2]*H[dx+2]: acc_c = acc_c + k * C_l(q)_c (a multiply, then an add), wsum = wsum + k;
+ *   C_{l+1}(p)_c = acc_c / wsum. The output is C_levels in the frame's format (half: round to nearest even; RGBA8:
+ *   the rule of rt4_frame_format) with the input's stored alpha; a pixel that is not filterable gets the input's
+ *   stored bits. */
+#define RT4_DENOISE_MAX_LEVELS 6
+typedef struct rt4_denoise_params {
+  int32_t levels;      /* 1 .. RT4_DENOISE_MAX_LEVELS */
+  float cos_min;       /* smallest dot of the two normals a tap may have */
+  float depth_tol;     /* largest |z_q - z_p| a tap may have, as a fraction of z_p */
+  float max_refl_prob; /* pixels whose primary hit reflects more often pass through unfiltered */
+} rt4_denoise_params;
+void rt4_denoise_params_default(rt4_denoise_params* p); /* 3, 0.9f, 0.1f, 0.5f */
+/* d_in and d_out (w x h frames of `format`, row strides in pixels) must not overlap: RT4_ERR_ARG. Asynchronous on
+ * `stream`. Intermediate levels and the repacked guide live in context-owned scratch (rt4_context_denoise_bytes):
+ * the first call that needs more waits for the stream and allocates. Ordered with the context's other launches. */
+int rt4_denoise_device(rt4_context* ctx, const void* d_in, int64_t in_stride_px, void* d_out, int64_t out_stride_px,
+                       int32_t format, int32_t w, int32_t h, const rt4_gbuffer_px* d_gbuf, int64_t gbuf_stride_px,
+                       const rt4_denoise_params* params, void* stream, char* err, size_t errlen);
+/* The same on host buffers (synchronous; output pixels outside [0,w) x [0,h) keep their bytes). */
+int rt4_denoise_host(rt4_context* ctx, const void* in, int64_t in_stride_px, void* out, int64_t out_stride_px,
+                     int32_t format, int32_t w, int32_t h, const rt4_gbuffer_px* gbuf, int64_t gbuf_stride_px,
+                     const rt4_denoise_params* params, char* err, size_t errlen);
+/* Bytes of the context's denoise scratch (0 before the first rt4_denoise_device call). */
+uint64_t rt4_context_denoise_bytes(const rt4_context* ctx);
 
 /* ---- diagnostics (used by the parity tests; not on the render path) ------------------------- */
 /* Bytes of the context's frame-colour scratch for pipelined frames (0 before any pipelined launch or

@@ -31,6 +31,11 @@ def symbols(dis):
             cur = out.setdefault(m.group(1), [])
         elif cur is not None and ln.strip() and not ln.startswith("Disassembly of section"):
             cur.append(" ".join(ADDR_COMMENT.sub("// ", ln).split()))
+    # objdump prints "..." for the zero bytes that pad a symbol up to the next one: every symbol ends with it except
+    # the section's last, which is another symbol once kernels are added behind it. Padding after the code is no code.
+    for text in out.values():
+        while text and text[-1] == "...":
+            text.pop()
     return out
 
 
