@@ -81,6 +81,9 @@ __device__ __forceinline__ float went_w(WEntry e) { return e; }
 #ifndef RT4_ORDER_PREPASS
 #define RT4_ORDER_PREPASS 1  // longest-first tile order from a primary-ray pre-pass (rt4_tile_order_kernel)
 #endif
+#ifndef RT4_FRAME_INNER
+#define RT4_FRAME_INNER 1  // pipelined launches: tile-major queue with the frames inside (rt4_trace_kernel FRAME_INNER); 0 = off
+#endif
 #ifndef RT4_SKY_PRETEST
 #define RT4_SKY_PRETEST 1
 #endif
@@ -387,8 +390,8 @@ struct KernelArgs {
   unsigned long long* eval_counter;  // evaluated find_intersection calls (primary-reuse launches), or null
   JobArgs jobs[RT4_MAX_SECTIONS];
   // Frames pipelined in one launch (rt4_render_frames_device): n_frames > 1 runs n_frames frames of job 0
-  // through one queue (queue item = frame x tile), frame f with seed frame_seed[f]; a finished pixel's
-  // tone-mapped colour goes to fcolor[f] and rt4_fold_frames_kernel blends the frames in order
+  // through one queue (queue item = frame x tile, in the order of claim_batch), frame f with seed
+  // frame_seed[f]; a finished pixel's tone-mapped colour goes to fcolor[f] and rt4_fold_frames_kernel blends the frames in order
   // (frame_part[f]) into the frame buffer afterwards. Pixel words then pack j | i << 13 | f << 26.
   int32_t n_frames;
   unsigned frame_tiles;  // tiles per frame
@@ -651,6 +654,11 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
   // (profiles/r03_ab.txt): hypercube +3.7 % at 2, all_primitives +4.6 % and the mirror room +1.4 % at 4,
   // but the sphere kernel with deferred exact tests -5..-7 %: it keeps one.
   constexpr unsigned CLAIM_TILES = static_cast<unsigned>(DEFER ? RT4_CLAIM_TILES_DEFER : RT4_CLAIM_TILES);
+  // Queue order of a pipelined launch: the open specialised kernels without a tiger hand the
+  // image out once, row-major, with all frames of a tile together, so the launch crosses from the sky rows to the
+  // ground once instead of once per frame (config 2 -2.4..-3.5 %, config 3 -1.7..-2.9 %; profiles/r08_ab.txt). The
+  // tiger, closed-room and generic kernels keep the frame-major queue and compile as before.
+  constexpr bool FRAME_INNER = RT4_FRAME_INNER && K != GENERIC && !(K & K_TIGER) && !phase_refill_of(K);
   uint32_t in_seed = useed;  // wave-uniform: the seed of the inbox's frame
   unsigned ring_n = 0;    // wave-uniform: outbox entries waiting to be written
   // The refill's wave-uniform state (ring_n, spare, in_next, the claimed tile) goes through rt4_uni where it is
@@ -741,8 +749,8 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
       base = spare & ~(BATCH - 1u);
       spare += BATCH - 1u;  // the next position, one tile fewer
     } else {
-      // several tiles per claim only in pipelined launches and before their last frame, so the drain at
-      // the end of the launch still hands out single tiles
+      // several items per claim only in pipelined launches and before their last frame_tiles items (the last
+      // frame of a frame-major queue), so the drain at the end of the launch still hands out single tiles
       const unsigned nt =
           (CLAIM_TILES > 1 && a.n_frames > 1 && (spare & ~(BATCH - 1u)) + a.frame_tiles * BATCH < total) ? CLAIM_TILES
                                                                                                          : 1u;
@@ -755,8 +763,14 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
     // a 64-pixel batch is one tile of one job (of one frame): wave-uniform here (scalar loads)
     unsigned pos = base >> 6, frame = 0;
     if (a.n_frames > 1) {
-      frame = pos / a.frame_tiles;
-      pos -= frame * a.frame_tiles;
+      if constexpr (FRAME_INNER) {  // tile-major, the frames inside: item = tile x n_frames + frame
+        const unsigned slot = pos / static_cast<unsigned>(a.n_frames);
+        frame = pos - slot * static_cast<unsigned>(a.n_frames);
+        pos = slot;
+      } else {  // frame-major: item = frame x frame_tiles + tile
+        frame = pos / a.frame_tiles;
+        pos -= frame * a.frame_tiles;
+      }
       in_seed = uni(static_cast<uint32_t>(a.frame_seed[frame]));
     }
     const unsigned btile = uni(order ? order[pos] : pos);
