@@ -11,7 +11,8 @@
 // cannot run in this environment (no desktop GL) and ships no tests, golden images or
 // fixtures. What IS pinned: the integer RNG against the survey's known-answer vectors (hash, first
 // rand() of two pixels: SURVEY.md §4), the sampler's domain properties (exhaustive 2^23 sweep), and
-// each intersector against closed-form geometry (tests/test_oracle.py).
+// each intersector against closed-form geometry (tests/test_oracle.py), and find_intersection and whole pixels
+// against an independent float64 restatement of the shader (tests/shader_f64.py, tests/test_shader_f64.py).
 //
 // fp32 semantics (shared with the kernel). GLSL leaves built-in precision to the
 // driver, so this restatement fixes one definition both sides follow bit for bit:

@@ -1,11 +1,17 @@
 """The CPU oracle against the known answers it can be pinned to (no GPU needed).
 
 Pins: the reference ships no tests or golden data, and its GLSL cannot run here,
-so images are "parity unpinned". What is pinned:
+so against the GL reference itself images are "parity unpinned". What is pinned here:
   * integer RNG: hash() and the first rand() values of two pixels (tests/golden/kat.json)
   * S^3 sampler: w_by_volume known answers + the exhaustive 2^23-input sweep statistics
   * intersectors: closed-form geometry (distances, normals) for every primitive kind
   * image invariants: sky-only pixels, emissive direct hits, colour range, alpha
+and in test_shader_f64.py, against an independent float64 restatement of the shader (shader_f64.py):
+  * find_intersection of every kind, composites and their quirks included: hit flag, winner, glow and refl_prob
+    equal, distance and normal within four times the restatement's own fp32-against-float64 difference
+  * whole pixels: the random path (per-pixel find_intersection counts: the rand() order, the seed carried over
+    bounces and samples, the row orientation) equal and the colour within the same kind of bound, over two
+    blended frames
 """
 import json
 import math
