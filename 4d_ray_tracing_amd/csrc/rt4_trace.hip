@@ -1342,6 +1342,17 @@ __global__ void rt4_find_kernel(const rt4_scene_desc* __restrict__ S, const Scen
   }
 }
 
+// final_light of n directions, one lane each (rt4_debug_final_light): the trace kernels' own device function on
+// the context's scene and aux block. drct: n x 4 floats, out: n x 3.
+__global__ void rt4_final_light_kernel(const rt4_scene_desc* __restrict__ S, const SceneAux* __restrict__ X,
+                                       const float* __restrict__ drct, float* __restrict__ out, int64_t n) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const V3 fl = final_light(S, X, ld4(drct + 4 * t));
+  float* o = out + 3 * t;
+  o[0] = fl.x; o[1] = fl.y; o[2] = fl.z;
+}
+
 // Tile order for the pixel queue (longest work first): one thread per 8x8 tile traces the primary ray
 // of the tile's centre pixel; tiles whose ray hits something go to the front of `order`, sky tiles to
 // the back. The queue hands tiles out in this order, so the slow tiles do not form the drain at the
@@ -2796,6 +2807,31 @@ int rt4_debug_find_intersection(rt4_context* ctx, const float* rays, float* out,
   if (dcol) (void)hipFree(dcol);
   if (e != hipSuccess) {
     rt4_set_err(err, errlen, "debug_find_intersection failed: %s", hipGetErrorString(e));
+    return RT4_ERR_HIP;
+  }
+  return RT4_OK;
+}
+
+int rt4_debug_final_light(rt4_context* ctx, const float* drct, float* out, int64_t n, char* err, size_t errlen) {
+  if (!ctx || !drct || !out || n < 0) return rt4_set_err(err, errlen, "bad argument"), RT4_ERR_ARG;
+  if (!ctx->has_scene) return rt4_set_err(err, errlen, "context has no scene"), RT4_ERR_ARG;
+  if (n == 0) return RT4_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  float *dd = nullptr, *dout = nullptr;
+  HIP_TRY(hipMalloc(&dd, n * 4 * sizeof(float)));
+  hipError_t e = hipMalloc(&dout, n * 3 * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(dd, drct, n * 4 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(rt4_final_light_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, 0, ctx->d_scene,
+                       scene_aux(ctx), dd, dout, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, dout, n * 3 * sizeof(float), hipMemcpyDeviceToHost);
+  (void)hipFree(dd);
+  if (dout) (void)hipFree(dout);
+  if (e != hipSuccess) {
+    rt4_set_err(err, errlen, "debug_final_light failed: %s", hipGetErrorString(e));
     return RT4_ERR_HIP;
   }
   return RT4_OK;

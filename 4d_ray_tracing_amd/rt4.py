@@ -199,6 +199,7 @@ def _load(path=None):
         "rt4_render_host": ([c_void_p, POINTER(Uniforms), POINTER(Region), c_void_p, c_int64, POINTER(c_uint64)] + E, c_int),
         "rt4_debug_eval": ([c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
         "rt4_debug_find_intersection": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
+        "rt4_debug_final_light": ([c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
         "rt4_context_kernel_shape": ([c_void_p], c_uint32),
         "rt4_debug_verify_sqrt": ([c_void_p, POINTER(c_uint64)] + E, c_int),
         "rt4_frame_format_bytes": ([c_int32], c_int32),
@@ -280,7 +281,8 @@ EXPORTED = (
     "rt4_band_plan rt4_bands_unpermute_device rt4_context_frame_scratch_bytes rt4_context_overlap_bytes rt4_context_reserve_overlap rt4_accum_save rt4_accum_info rt4_accum_load rt4_write_png "
     "rt4_accum_save_key rt4_accum_key rt4_accum_key_of "
     "rt4_scene_surface_count rt4_scene_surface rt4_render_gbuffer_device rt4_render_gbuffer_host "
-    "rt4_denoise_params_default rt4_denoise_device rt4_denoise_host rt4_context_denoise_bytes"
+    "rt4_denoise_params_default rt4_denoise_device rt4_denoise_host rt4_context_denoise_bytes "
+    "rt4_debug_final_light"
 ).split()
 
 if ctypes.sizeof(SceneDesc) != lib.rt4_scene_desc_size() or ctypes.sizeof(Uniforms) != lib.rt4_uniforms_size():
@@ -852,3 +854,14 @@ class Tracer:
         _check(self._lib.rt4_debug_find_intersection(self._h, c_void_p(rays.ctypes.data), c_void_p(out.ctypes.data),
                                                c_void_p(col.ctypes.data), rays.shape[0], err, len(err)), err)
         return out, col
+
+    def debug_final_light(self, drct):
+        """final_light of the trace kernels for directions (n, 4), as they are (rt4_debug_final_light): (n, 3)."""
+        import numpy as np
+
+        drct = np.ascontiguousarray(drct, dtype=np.float32).reshape(-1, 4)
+        out = np.empty((drct.shape[0], 3), np.float32)
+        err = _errbuf()
+        _check(self._lib.rt4_debug_final_light(self._h, c_void_p(drct.ctypes.data), c_void_p(out.ctypes.data),
+                                               drct.shape[0], err, len(err)), err)
+        return out

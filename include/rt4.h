@@ -582,6 +582,11 @@ int rt4_debug_eval(rt4_context* ctx, int fn, const float* in, float* out, int32_
 int rt4_debug_find_intersection(rt4_context* ctx, const float* rays, float* out, float* out_color, int64_t n,
                                 char* err, size_t errlen);
 
+/* Runs the trace kernels' final_light (shader.frag:454-468 behind the sky shortcuts of the context's scene) for n
+ * escaping directions, one lane each. drct: n x 4 floats, as they are (not normalised); out: n x 3 floats.
+ * Synchronous; host buffers. RT4_ERR_ARG (nothing written) for a NULL pointer, n < 0 or a context without a scene. */
+int rt4_debug_final_light(rt4_context* ctx, const float* drct, float* out, int64_t n, char* err, size_t errlen);
+
 /* Counts the 32-bit patterns x for which the kernel's sqrt (fast path without input scaling) differs
  * from the IEEE square root; 0 expected. Exhaustive over all 2^32 inputs on the device (~10 ms). */
 int rt4_debug_verify_sqrt(rt4_context* ctx, uint64_t* mismatches, char* err, size_t errlen);

@@ -655,6 +655,16 @@ int oracle_find_intersection(const rt4_scene_desc* s, const float* rays, float* 
   return RT4_OK;
 }
 
+// final_light (shader.frag:454-468) for n directions as they are; drct: n x 4, out: n x 3.
+int oracle_final_light(const rt4_scene_desc* s, const float* drct, float* out, int64_t n) {
+  if (!s || !drct || !out || n < 0) return RT4_ERR_ARG;
+  for (int64_t i = 0; i < n; i++) {
+    const V3<float> l = final_light(*s, v4<float>(drct + 4 * i));
+    out[3 * i] = l.x; out[3 * i + 1] = l.y; out[3 * i + 2] = l.z;
+  }
+  return RT4_OK;
+}
+
 // One diffuse direction draw from a given RNG state (for sampler tests): returns the direction and
 // the advanced counter. state[0]=uint_seed, state[1]=rand_iter_seed, state[2]=bits(sx), state[3]=bits(sy).
 void oracle_rand_drct(uint32_t* state, float* out4) {

@@ -78,6 +78,18 @@ def find_intersection(scene_desc, rays):
     return out, col
 
 
+def final_light(scene_desc, drct, native=False):
+    """oracle_final_light: final_light (shader.frag:454-468) of directions (n, 4), as they are: (n, 3)."""
+    lib_ = lib(native)
+    lib_.oracle_final_light.argtypes = [c_void_p, c_void_p, c_void_p, c_int64]
+    lib_.oracle_final_light.restype = ctypes.c_int
+    drct = np.ascontiguousarray(drct, dtype=np.float32).reshape(-1, 4)
+    out = np.empty((drct.shape[0], 3), np.float32)
+    st = lib_.oracle_final_light(ctypes.addressof(scene_desc), drct.ctypes.data, out.ctypes.data, drct.shape[0])
+    assert st == 0
+    return out
+
+
 def render(scene_desc, uniforms, reg, frame=None, threads=None, count_ops=False, pixel_counts=False, native=False):
     """Renders `reg` into frame (h, w, 4) float32 (zeros if None). Returns (frame, n_inter, ops, counts).
     native=True: the native-math build (glibc built-ins, unfused), for the sensitivity report only."""
