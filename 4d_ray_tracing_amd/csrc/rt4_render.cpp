@@ -23,6 +23,10 @@
 //                   [--denoise [levels]]  (next to every image also <name>_dn.<ext>: the final frame through the
 //                   edge-stopping filter, rt4_render_gbuffer_device of the last camera pose + rt4_denoise_device; the
 //                   accumulator itself is never filtered. One GPU only: not with --gpus)
+//                   [--reproject]  (temporal reprojection: one rt4_temporal per section takes every frame, so the
+//                   accumulated image survives --keys / --move-seconds instead of restarting; the images written are
+//                   the temporal images, --denoise filters them with the temporal G-buffer. A resting camera gives the
+//                   image of a run without the flag. Not with --gpus, --resume, --checkpoint, --frame-by-frame)
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -301,6 +305,7 @@ int main(int argc, char** argv) {
   std::string resume_path, checkpoint_path;
   bool png = false, rehearse = false, raw = false;
   int denoise_levels = 0;  // --denoise: 0 = off
+  bool reproject = false;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -327,6 +332,7 @@ int main(int argc, char** argv) {
     else if (a == "--png") png = true;
     else if (a == "--raw") raw = true;
     else if (a == "--rehearse") rehearse = true;
+    else if (a == "--reproject") reproject = true;
     else if (a == "--denoise") {
       rt4_denoise_params dp;
       rt4_denoise_params_default(&dp);
@@ -336,6 +342,10 @@ int main(int argc, char** argv) {
     }
     else die("unknown argument", a.c_str());
   }
+  if (reproject && gpus > 0) die("--reproject", "not with --gpus: the temporal image lives on one GPU");
+  if (reproject && (!resume_path.empty() || !checkpoint_path.empty()))
+    die("--reproject", "not with --resume / --checkpoint: a checkpoint holds no per-pixel history");
+  if (reproject && frame_by_frame) die("--reproject", "not with --frame-by-frame: every temporal frame is a launch of its own");
   const int32_t format = fmt_name == "f16" ? RT4_FRAME_RGBA16F : fmt_name == "rgba8" ? RT4_FRAME_RGBA8 : RT4_FRAME_RGBA32F;
   char err[1024] = {0};
   rt4_properties* props = nullptr;
@@ -459,7 +469,10 @@ int main(int argc, char** argv) {
 
   // One section and a resting camera (progressive accumulation): the frames go to the library in one
   // rt4_render_frames_device call (pipelined through one pixel queue; the same final image).
-  const bool pipelined = n_img == 1 && !(keys && move_seconds > 0.0f) && !frame_by_frame;
+  const bool pipelined = n_img == 1 && !(keys && move_seconds > 0.0f) && !frame_by_frame && !reproject;
+  rt4_temporal* temporal[3] = {nullptr, nullptr, nullptr};  // --reproject: one per section
+  for (int q = 0; q < n_img && reproject; q++)
+    RT4_CHECK(rt4_temporal_create(ctx, cw[q], ch[q], format, &temporal[q], err, sizeof err));
   std::vector<rt4_uniforms> us;
   if (pipelined) {
     // the frame-colour scratch only when frames are actually pipelined (>= 2 frames, a scene that does
@@ -492,10 +505,14 @@ int main(int argc, char** argv) {
       jobs[q].d_frame = d_frame[q];
       jobs[q].row_stride_px = cw[q];
       last_u[q] = jobs[q].u;
+      if (reproject) RT4_CHECK(rt4_temporal_frame_device(temporal[q], &jobs[q].u, nullptr, d_count, nullptr, err, sizeof err));
     }
-    RT4_CHECK(rt4_render_sections_device(ctx, jobs, n_img, format, d_count, nullptr, err, sizeof err));
+    if (!reproject) RT4_CHECK(rt4_render_sections_device(ctx, jobs, n_img, format, d_count, nullptr, err, sizeof err));
     if (keys && move_seconds > 0.0f) rt4_camera_move(&cam, keys, move_seconds);  // move(seconds), main.cpp:95-96
   }
+  for (int q = 0; q < n_img && reproject; q++)  // the images written are the temporal images
+    HIP_CHECK(hipMemcpyAsync(d_frame[q], rt4_temporal_image(temporal[q]), static_cast<size_t>(cw[q]) * ch[q] * px,
+                             hipMemcpyDeviceToDevice, nullptr));
   HIP_CHECK(hipEventRecord(e1, nullptr));
   HIP_CHECK(hipEventSynchronize(e1));
   float ms = 0.0f;
@@ -523,9 +540,10 @@ int main(int argc, char** argv) {
       rt4_denoise_params dp;
       rt4_denoise_params_default(&dp);
       dp.levels = denoise_levels;
-      RT4_CHECK(rt4_render_gbuffer_device(ctx, &last_u[q], &reg, d_gbuf, cw[q], nullptr, err, sizeof err));
-      RT4_CHECK(rt4_denoise_device(ctx, d_frame[q], cw[q], d_dn, cw[q], format, cw[q], ch[q], d_gbuf, cw[q], &dp, nullptr, err,
-                                   sizeof err));
+      // --reproject: the temporal object already holds the G-buffer of the last pose
+      if (!reproject) RT4_CHECK(rt4_render_gbuffer_device(ctx, &last_u[q], &reg, d_gbuf, cw[q], nullptr, err, sizeof err));
+      RT4_CHECK(rt4_denoise_device(ctx, d_frame[q], cw[q], d_dn, cw[q], format, cw[q], ch[q],
+                                   reproject ? rt4_temporal_gbuffer(temporal[q]) : d_gbuf, cw[q], &dp, nullptr, err, sizeof err));
       HIP_CHECK(hipDeviceSynchronize());
       std::vector<unsigned char> dn(host.size());
       HIP_CHECK(hipMemcpy(dn.data(), d_dn, dn.size(), hipMemcpyDeviceToHost));
@@ -546,6 +564,7 @@ int main(int argc, char** argv) {
   std::printf("frames %d, images %d, intersections %llu, %.3f ms/frame, %.3e intersections/s\n", frames, n_img,
               count, ms / frames, static_cast<double>(count) / (ms * 1e-3));
 
+  for (int q = 0; q < n_img; q++) rt4_temporal_destroy(temporal[q]);
   for (int q = 0; q < n_img; q++) (void)hipFree(d_frame[q]);
   (void)hipFree(d_count);
   rt4_context_destroy(ctx);

@@ -154,6 +154,11 @@ class DenoiseParams(Structure):  # rt4.h rt4_denoise_params
 DENOISE_MAX_LEVELS = 6
 
 
+class ReprojectParams(Structure):  # rt4.h rt4_reproject_params
+    _fields_ = [("cos_min", c_float), ("plane_tol", c_float), ("slice_tol", c_float), ("max_refl_prob", c_float),
+                ("max_history", c_int32)]
+
+
 def _gbuffer_dtype():
     import numpy as np
 
@@ -250,6 +255,24 @@ def _load(path=None):
         "rt4_denoise_host": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64,
                               POINTER(DenoiseParams)] + E, c_int),
         "rt4_context_denoise_bytes": ([c_void_p], c_uint64),
+        "rt4_reproject_params_default": ([POINTER(ReprojectParams)], None),
+        "rt4_reproject_device": ([c_void_p, POINTER(Uniforms), c_void_p, c_int64, POINTER(Uniforms), c_void_p, c_int64,
+                                  c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32,
+                                  c_int32, c_int32, POINTER(ReprojectParams), c_void_p] + E, c_int),
+        "rt4_reproject_host": ([c_void_p, POINTER(Uniforms), c_void_p, c_int64, POINTER(Uniforms), c_void_p, c_int64,
+                                c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32,
+                                c_int32, c_int32, POINTER(ReprojectParams)] + E, c_int),
+        "rt4_temporal_blend_device": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32,
+                                       c_int32, c_void_p] + E, c_int),
+        "rt4_temporal_create": ([c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)] + E, c_int),
+        "rt4_temporal_destroy": ([c_void_p], None),
+        "rt4_temporal_reset": ([c_void_p], None),
+        "rt4_temporal_frame_device": ([c_void_p, POINTER(Uniforms), POINTER(ReprojectParams), c_void_p, c_void_p] + E, c_int),
+        "rt4_temporal_image": ([c_void_p], c_void_p),
+        "rt4_temporal_history": ([c_void_p], c_void_p),
+        "rt4_temporal_gbuffer": ([c_void_p], c_void_p),
+        "rt4_temporal_read_host": ([c_void_p, c_void_p, c_void_p, c_void_p] + E, c_int),
+        "rt4_temporal_bytes": ([c_void_p], c_uint64),
     }
     tolerant = os.environ.get("RT4_AB_TOLERANT") == "1"  # tools/abtest.sh: older builds lack newer exports
     for name, (argtypes, restype) in sig.items():
@@ -282,7 +305,10 @@ EXPORTED = (
     "rt4_accum_save_key rt4_accum_key rt4_accum_key_of "
     "rt4_scene_surface_count rt4_scene_surface rt4_render_gbuffer_device rt4_render_gbuffer_host "
     "rt4_denoise_params_default rt4_denoise_device rt4_denoise_host rt4_context_denoise_bytes "
-    "rt4_debug_final_light"
+    "rt4_debug_final_light "
+    "rt4_reproject_params_default rt4_reproject_device rt4_reproject_host rt4_temporal_blend_device rt4_temporal_create "
+    "rt4_temporal_destroy rt4_temporal_reset rt4_temporal_frame_device rt4_temporal_image rt4_temporal_history "
+    "rt4_temporal_gbuffer rt4_temporal_read_host rt4_temporal_bytes"
 ).split()
 
 if ctypes.sizeof(SceneDesc) != lib.rt4_scene_desc_size() or ctypes.sizeof(Uniforms) != lib.rt4_uniforms_size():
@@ -474,6 +500,18 @@ def denoise_params(levels: int | None = None, cos_min: float | None = None, dept
     p = DenoiseParams()
     lib.rt4_denoise_params_default(byref(p))
     for name, v in (("levels", levels), ("cos_min", cos_min), ("depth_tol", depth_tol), ("max_refl_prob", max_refl_prob)):
+        if v is not None:
+            setattr(p, name, v)
+    return p
+
+
+def reproject_params(cos_min: float | None = None, plane_tol: float | None = None, slice_tol: float | None = None,
+                     max_refl_prob: float | None = None, max_history: int | None = None) -> ReprojectParams:
+    """rt4_reproject_params_default (0.9, 0.02, 0.01, 0.5, 255) with the given fields replaced."""
+    p = ReprojectParams()
+    lib.rt4_reproject_params_default(byref(p))
+    for name, v in (("cos_min", cos_min), ("plane_tol", plane_tol), ("slice_tol", slice_tol),
+                    ("max_refl_prob", max_refl_prob), ("max_history", max_history)):
         if v is not None:
             setattr(p, name, v)
     return p
@@ -800,6 +838,58 @@ class Tracer:
         """Bytes of the context's denoise scratch (rt4.h rt4_context_denoise_bytes)."""
         return int(self._lib.rt4_context_denoise_bytes(self._h))
 
+    def reproject_device(self, u_cur: Uniforms, gcur_ptr: int, gcur_stride: int, u_prev: Uniforms, gprev_ptr: int,
+                         gprev_stride: int, accp_ptr: int, accp_stride: int, histp_ptr: int, histp_stride: int, acco_ptr: int,
+                         acco_stride: int, histo_ptr: int, histo_stride: int, fmt: int, w: int, h: int,
+                         params: ReprojectParams | None = None, stream: int = 0) -> None:
+        """Asynchronous temporal reprojection of a device image and its history from the view of u_prev into the view
+        of u_cur (rt4_reproject_device)."""
+        p = params if params is not None else reproject_params()
+        err = _errbuf()
+        _check(self._lib.rt4_reproject_device(
+            self._h, byref(u_cur) if u_cur is not None else None, c_void_p(gcur_ptr or None), gcur_stride,
+            byref(u_prev) if u_prev is not None else None, c_void_p(gprev_ptr or None), gprev_stride, c_void_p(accp_ptr or None),
+            accp_stride, c_void_p(histp_ptr or None), histp_stride, c_void_p(acco_ptr or None), acco_stride,
+            c_void_p(histo_ptr or None), histo_stride, fmt, w, h, byref(p), c_void_p(stream or None), err, len(err)), err)
+
+    def reproject_host(self, u_cur: Uniforms, gcur, u_prev: Uniforms, gprev, acc_prev, hist_prev,
+                       params: ReprojectParams | None = None, acc_out=None, hist_out=None, fmt: int | None = None,
+                       w: int | None = None):
+        """Synchronous reprojection of host arrays: G-buffers (h, stride) of GBUFFER_DTYPE, acc_prev (h, stride, 4) of
+        the format's dtype, hist_prev (h, stride) int32; w: the image width when rows are padded. Returns (acc_out,
+        hist_out) (new arrays if None)."""
+        import numpy as np
+
+        if fmt is None:
+            fmt = {np.dtype("float32"): FRAME_RGBA32F, np.dtype("float16"): FRAME_RGBA16F,
+                   np.dtype("uint8"): FRAME_RGBA8}[acc_prev.dtype]
+        h = acc_prev.shape[0]
+        w = acc_prev.shape[1] if w is None else w
+        if acc_out is None:
+            acc_out = np.zeros((h, w, 4), acc_prev.dtype)
+        if hist_out is None:
+            hist_out = np.zeros((h, w), np.int32)
+        for a, dt in ((gcur, GBUFFER_DTYPE), (gprev, GBUFFER_DTYPE), (acc_prev, np.dtype(FRAME_NUMPY[fmt])),
+                      (acc_out, np.dtype(FRAME_NUMPY[fmt])), (hist_prev, np.dtype(np.int32)), (hist_out, np.dtype(np.int32))):
+            assert a.dtype == dt and a.flags["C_CONTIGUOUS"] and a.shape[0] == h
+        p = params if params is not None else reproject_params()
+        err = _errbuf()
+        _check(self._lib.rt4_reproject_host(
+            self._h, byref(u_cur), c_void_p(gcur.ctypes.data), gcur.shape[1], byref(u_prev), c_void_p(gprev.ctypes.data),
+            gprev.shape[1], c_void_p(acc_prev.ctypes.data), acc_prev.shape[1], c_void_p(hist_prev.ctypes.data),
+            hist_prev.shape[1], c_void_p(acc_out.ctypes.data), acc_out.shape[1], c_void_p(hist_out.ctypes.data),
+            hist_out.shape[1], fmt, w, h, byref(p), err, len(err)), err)
+        return acc_out, hist_out
+
+    def temporal_blend_device(self, new_ptr: int, new_stride: int, acc_ptr: int, acc_stride: int, fmt: int, hist_ptr: int,
+                              hist_stride: int, w: int, h: int, stream: int = 0) -> None:
+        """Asynchronous per-pixel progressive blend of an RGBA32F sample frame into a device accumulator of `fmt`,
+        part = 1 / (history + 1) per pixel; the history counts up (rt4_temporal_blend_device)."""
+        err = _errbuf()
+        _check(self._lib.rt4_temporal_blend_device(self._h, c_void_p(new_ptr or None), new_stride, c_void_p(acc_ptr or None),
+                                                   acc_stride, fmt, c_void_p(hist_ptr or None), hist_stride, w, h,
+                                                   c_void_p(stream or None), err, len(err)), err)
+
     @property
     def kernel_shape(self) -> int:
         """Shape code of the trace kernel the scene runs on (rt4.h rt4_context_kernel_shape)."""
@@ -865,3 +955,71 @@ class Tracer:
         _check(self._lib.rt4_debug_final_light(self._h, c_void_p(drct.ctypes.data), c_void_p(out.ctypes.data),
                                                drct.shape[0], err, len(err)), err)
         return out
+
+
+class Temporal:
+    """rt4_temporal: a progressive image that survives camera moves. Every frame() renders one sample frame and
+    blends it per pixel; when the pose changed, the image and its per-pixel frame counts are first reprojected into
+    the new view (rt4.h rt4_temporal_frame_device). Close it before its Tracer. After Tracer.set_scene call reset()."""
+
+    def __init__(self, tracer: Tracer, w: int, h: int, fmt: int = FRAME_RGBA32F):
+        self._lib = tracer._lib
+        self._tracer = tracer  # keeps the context alive
+        self.w, self.h, self.fmt = w, h, fmt
+        t = c_void_p()
+        err = _errbuf()
+        _check(self._lib.rt4_temporal_create(tracer._h, w, h, fmt, byref(t), err, len(err)), err)
+        self._t = t
+
+    def close(self):
+        if getattr(self, "_t", None):
+            if getattr(self._tracer, "_h", None):  # a closed Tracer took the device buffers' context with it
+                self._lib.rt4_temporal_destroy(self._t)
+            self._t = None
+
+    __del__ = close
+
+    def reset(self) -> None:
+        self._lib.rt4_temporal_reset(self._t)
+
+    def frame(self, u: Uniforms, params: ReprojectParams | None = None, counter_ptr: int = 0, stream: int = 0) -> None:
+        """Asynchronous: one frame of `u` (u.part is ignored)."""
+        err = _errbuf()
+        _check(self._lib.rt4_temporal_frame_device(self._t, byref(u), byref(params) if params is not None else None,
+                                                   c_void_p(counter_ptr or None), c_void_p(stream or None), err, len(err)), err)
+
+    # device pointers (row stride w); they change with every frame()
+    def image_ptr(self) -> int:
+        return int(self._lib.rt4_temporal_image(self._t) or 0)
+
+    def history_ptr(self) -> int:
+        return int(self._lib.rt4_temporal_history(self._t) or 0)
+
+    def gbuffer_ptr(self) -> int:
+        return int(self._lib.rt4_temporal_gbuffer(self._t) or 0)
+
+    def bytes(self) -> int:
+        return int(self._lib.rt4_temporal_bytes(self._t))
+
+    def _read(self, which: int):
+        import numpy as np
+
+        out = [np.zeros((self.h, self.w, 4), FRAME_NUMPY[self.fmt]), np.zeros((self.h, self.w), np.int32),
+               np.zeros((self.h, self.w), GBUFFER_DTYPE)][which]
+        ptrs = [None, None, None]
+        ptrs[which] = c_void_p(out.ctypes.data)
+        err = _errbuf()
+        _check(self._lib.rt4_temporal_read_host(self._t, ptrs[0], ptrs[1], ptrs[2], err, len(err)), err)
+        return out
+
+    def image(self):
+        """Synchronous: the current image on the host, (h, w, 4) of the format's dtype."""
+        return self._read(0)
+
+    def history(self):
+        """Synchronous: the frames blended into every pixel, (h, w) int32."""
+        return self._read(1)
+
+    def gbuffer(self):
+        """Synchronous: the G-buffer of the last frame's pose, (h, w) of GBUFFER_DTYPE."""
+        return self._read(2)

@@ -552,6 +552,97 @@ int rt4_denoise_host(rt4_context* ctx, const void* in, int64_t in_stride_px, voi
 /* Bytes of the context's denoise scratch (0 before the first rt4_denoise_device call). */
 uint64_t rt4_context_denoise_bytes(const rt4_context* ctx);
 
+/* ---- temporal reprojection (no reference counterpart) ------------------------
+ * The reference restarts its progressive image whenever the camera moves (controls.cpp:132,181,190). Reprojection
+ * carries every pixel's accumulated colour and its frame count (the history) to where its surface point appears in
+ * the new view, and restarts only the pixels whose history is invalid. All images are whole frames [0,w) x [0,h);
+ * u_cur->resolution and u_prev->resolution must equal (w, h). G_cur / G_prev are the G-buffers of u_cur / u_prev
+ * (rt4_render_gbuffer_device), acc_prev / hist_prev the image and history of the old view.
+ * Definition (fp32 round-to-nearest, no contraction, division and sqrt correctly rounded; dot is the fma chain of
+ * DESIGN.md §3, mad(a,s,b) one fma per component; the kernel matches it bit for bit). For pixel p = (j, i), g = G_cur(p):
+ *   1. p is eligible iff g.surface >= 0 && g.refl_prob <= max_refl_prob && fabsf(g.depth) < inf.
+ *   2. d = the primary direction of p under u_cur, op for op as rt4_render_gbuffer_device builds it;
+ *      X = mad(d, g.depth, focus_cur).
+ *   3. v = X - focus_prev; F = vec_to_mtr_prev, T = top_drct_prev, R = right_drct_prev (assumed mutually orthogonal,
+ *      T and R unit: every rt4_section_basis). a = dot(v,F) / dot(F,F), a > 0 required; t = dot(v,T), r = dot(v,R);
+ *      e = mad(R, -r, mad(T, -t, mad(F, -a, v))), dot(e,e) <= (slice_tol*slice_tol) * dot(v,v) required (the 4D test:
+ *      the point still lies in the 3D slice the old camera saw); dv = sqrt(dot(v,v)).
+ *   4. mx = r / a, my = t / a; sx = mx / mtr_prev.x + 0.5f, sy = 0.5f - my / mtr_prev.y; fx = sx * res.x - 0.5f,
+ *      fy = sy * res.y - 0.5f (a multiply, then a subtract); fx > -1 && fx < w && fy > -1 && fy < h required (false
+ *      for NaN); x0 = floorf(fx), y0 = floorf(fy), ax = fx - x0, ay = fy - y0.
+ *   5. Taps ty = 0,1 (outer), tx = 0,1 (inner): q = (x0+tx, y0+ty), k = (tx ? ax : 1-ax) * (ty ? ay : 1-ay). A tap
+ *      counts iff q is inside the image, k > 0, hist_prev(q) > 0, G_prev(q).surface == g.surface,
+ *      dot(n_p, n_q) >= cos_min and fabsf(dot(n_p, X_q - X)) <= plane_tol * dv, where X_q = mad(d_q, z_q, focus_prev),
+ *      d_q the primary direction of q under u_prev and z_q = G_prev(q).depth (the distance of the old hit point from
+ *      the new hit's tangent plane; a depth difference fails on surfaces seen at grazing angles). A counted tap adds
+ *      acc_c = acc_c + k * C(q)_c (a multiply, then an add; C decoded as in the filter), wsum = wsum + k,
+ *      nmin = min(nmin, hist_prev(q)).
+ *   6. wsum > 0: the colour acc / wsum in the frame's format (fma(c, 1, 0), then half: round to nearest even; RGBA8:
+ *      the rule of rt4_frame_format) with alpha 1, and hist_out = min(nmin, max_history). Every other case: the zero
+ *      colour with alpha 1 and hist_out = 0. */
+typedef struct rt4_reproject_params {
+  float cos_min;       /* smallest dot(n_p, n_q) a tap may have */
+  float plane_tol;     /* largest distance of the old hit point from the new hit's tangent plane, as a fraction of dv */
+  float slice_tol;     /* largest out-of-slice distance of the hit point from the old camera's 3D slice, as a fraction of |v| */
+  float max_refl_prob; /* pixels whose primary hit reflects more often restart */
+  int32_t max_history; /* cap of the history length carried over (>= 1) */
+} rt4_reproject_params;
+/* 0.9f, 0.02f, 0.01f, 0.5f, 255. Starting points: nothing has been measured behind these values. */
+void rt4_reproject_params_default(rt4_reproject_params* p);
+/* Strides in elements of their image (G-buffer records, pixels, int32). RT4_ERR_ARG, nothing written, for a NULL
+ * pointer, an unknown format, a resolution other than (w, h), a stride below w, a misaligned pointer (G-buffers 16 B,
+ * frames their pixel size, histories 4 B), max_history < 1, or an output that overlaps an input or the other output.
+ * Asynchronous on `stream`, no allocation. Ordered with the context's other launches. */
+int rt4_reproject_device(rt4_context* ctx, const rt4_uniforms* u_cur, const rt4_gbuffer_px* d_gcur, int64_t gcur_stride,
+                         const rt4_uniforms* u_prev, const rt4_gbuffer_px* d_gprev, int64_t gprev_stride,
+                         const void* d_acc_prev, int64_t accp_stride, const int32_t* d_hist_prev, int64_t histp_stride,
+                         void* d_acc_out, int64_t acco_stride, int32_t* d_hist_out, int64_t histo_stride, int32_t format,
+                         int32_t w, int32_t h, const rt4_reproject_params* params, void* stream, char* err, size_t errlen);
+/* The same on host buffers (synchronous; output bytes outside [0,w) x [0,h) keep their values). */
+int rt4_reproject_host(rt4_context* ctx, const rt4_uniforms* u_cur, const rt4_gbuffer_px* gcur, int64_t gcur_stride,
+                       const rt4_uniforms* u_prev, const rt4_gbuffer_px* gprev, int64_t gprev_stride, const void* acc_prev,
+                       int64_t accp_stride, const int32_t* hist_prev, int64_t histp_stride, void* acc_out, int64_t acco_stride,
+                       int32_t* hist_out, int64_t histo_stride, int32_t format, int32_t w, int32_t h,
+                       const rt4_reproject_params* params, char* err, size_t errlen);
+
+/* The progressive blend with a frame count per pixel. For every pixel: n = hist(p) + 1 (saturating at INT32_MAX;
+ * hist(p) >= 0), part = 1.0f / (float)n, acc(p) = mix(acc(p), new(p).rgb, part) with the ops and roundings of
+ * rt4_render_device_ex in `format` (alpha 1), hist(p) = n. d_new is RGBA32F: a frame rendered with part = 1 into a
+ * buffer of finite values holds the tone-mapped colour itself, so with a uniform history this continues the plain
+ * progressive image bit for bit. The three images must not overlap (RT4_ERR_ARG). Asynchronous, no allocation. */
+int rt4_temporal_blend_device(rt4_context* ctx, const float* d_new_rgba32f, int64_t new_stride, void* d_acc,
+                              int64_t acc_stride, int32_t format, int32_t* d_hist, int64_t hist_stride, int32_t w, int32_t h,
+                              void* stream, char* err, size_t errlen);
+
+/* The two together, with the state they need: two accumulators in `format`, two histories, two G-buffers, one RGBA32F
+ * sample frame and the previous frame's uniforms, all allocated at creation (rt4_temporal_bytes). Destroy it before
+ * its context. The scene must not change between frames: after rt4_context_set_scene call rt4_temporal_reset. */
+typedef struct rt4_temporal rt4_temporal;
+int rt4_temporal_create(rt4_context* ctx, int32_t w, int32_t h, int32_t format, rt4_temporal** out, char* err, size_t errlen);
+void rt4_temporal_destroy(rt4_temporal* t); /* waits for the context's launches in flight */
+/* The next frame starts over (history 0), as the first frame after creation does. */
+void rt4_temporal_reset(rt4_temporal* t);
+/* One frame of `u` (u->resolution must be (w, h); u->part is ignored; params NULL = the defaults):
+ *   (a) the first frame after create / reset: the G-buffer of u; the history is 0;
+ *   (b) otherwise, if the pose of u (the bytes of resolution, mtr_sizes, focus, vec_to_mtr, top_drct, right_drct)
+ *       differs from the previous frame's: the G-buffer of u, then image and history reprojected into the other pair
+ *       of buffers, which becomes the current one; a resting camera pays for neither;
+ *   (c) u with part = 1 into the sample frame through rt4_render_device_ex (d_counter counts as usual);
+ *   (d) rt4_temporal_blend_device into the current image.
+ * Asynchronous on `stream`: no allocation here, no synchronisation (the render's own buffers as rt4_render_device). A
+ * resting camera's image equals the plain progressive run bit for bit. */
+int rt4_temporal_frame_device(rt4_temporal* t, const rt4_uniforms* u, const rt4_reproject_params* params,
+                              unsigned long long* d_counter, void* stream, char* err, size_t errlen);
+/* Device pointers of the current image (`format`), its history and the G-buffer of the last frame's pose (so
+ * rt4_denoise_device composes with them), each w x h with row stride w. They change with every frame call. */
+void* rt4_temporal_image(const rt4_temporal* t);
+int32_t* rt4_temporal_history(const rt4_temporal* t);
+const rt4_gbuffer_px* rt4_temporal_gbuffer(const rt4_temporal* t);
+/* The three copied to host buffers of w x h elements (any may be NULL). Synchronous: waits for the context's launches. */
+int rt4_temporal_read_host(rt4_temporal* t, void* image, int32_t* history, rt4_gbuffer_px* gbuf, char* err, size_t errlen);
+/* Device bytes the object owns. */
+uint64_t rt4_temporal_bytes(const rt4_temporal* t);
+
 /* ---- diagnostics (used by the parity tests; not on the render path) ------------------------- */
 /* Bytes of the context's frame-colour scratch for pipelined frames (0 before any pipelined launch or
  * reservation; a scene that runs frame by frame never allocates it). */
