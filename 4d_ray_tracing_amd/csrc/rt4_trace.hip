@@ -122,6 +122,16 @@ __device__ __forceinline__ float went_w(WEntry e) { return e; }
 #ifndef RT4_DEFER_WAIT
 #define RT4_DEFER_WAIT 4
 #endif
+#ifndef RT4_DEFER_SHADE
+// Deferred hit shading in the deferred-sphere kernels: a wave shades its hit lanes only once at
+// least RT4_DEFER_SHADE of its lanes hold a hit, or after RT4_DEFER_SHADE_WAIT iterations; the hit lanes that wait
+// park and redo the find on the same ray; 0 = off. Config 2 -6.5 % at 32 / 2; 8 gains 1 %, 16 6 %, 24 to 48 the
+// same as 32, 64 and waits of 3 or 4 slightly less (profiles/r09_ab.txt).
+#define RT4_DEFER_SHADE 32
+#endif
+#ifndef RT4_DEFER_SHADE_WAIT
+#define RT4_DEFER_SHADE_WAIT 2
+#endif
 #ifndef RT4_LSUM_REG
 #define RT4_LSUM_REG 1
 #endif
@@ -568,6 +578,11 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
           ? static_cast<unsigned>((K & K_TIGER) ? RT4_REFILL_OPEN_TIGER : RT4_REFILL_MIN_OPEN)
           : REFILL_MIN;
   int defer_age = 0;  // wave-uniform: iterations since the wave's parked lanes were first parked
+  // Deferred hit shading (the DEFER kernels): the hit path of shade() is the loop's largest
+  // divergent region and costs the wave the same on one lane as on 64, so a wave whose find left only a few
+  // hit lanes parks them (no shading, no count, no random number) until a fuller trip; see the rule at the find.
+  constexpr bool SDEFER = DEFER && RT4_DEFER_SHADE > 0;
+  int shade_age = 0;  // wave-uniform: iterations since the wave's parked hit lanes were first parked
   // Wave clock (closed scenes): while almost every path of the wave runs all R + 1 bounces
   // (early ends <= 1/32 of the sample ends, a leaky count), samples start only every R + 1 iterations, so
   // the lanes stay in lockstep bounce for bounce however long the launch; otherwise the phase rule above.
@@ -1058,6 +1073,49 @@ __global__ __launch_bounds__(256, min_waves_of(K, REUSE, LUT)) void rt4_trace_ke
         defer_age = 0;
       }
       if (active && !parked) c = find_rest<K>(S, X, P, ray, exact_pending<K>(X, P, ray, pend, inter));
+      if constexpr (SDEFER) {
+        // Deferred hit shading: the hit lanes (unparked, active, candidate a hit) are shaded now when
+        //  (a) at least RT4_DEFER_SHADE lanes of the wave are hit lanes, or
+        //  (b) a hit lane's candidate came through an exact test this iteration (run: every pending lane ran its
+        //      tests, so these are the hit lanes with a pending sphere), or
+        //  (c) every unparked active lane is a hit lane (nothing else would use the iteration), or
+        //  (d) shade_age has reached RT4_DEFER_SHADE_WAIT;
+        // otherwise they park: no shade(), no count, no random number, no state kept. Miss lanes shade at once.
+        // Same bits: a parked lane's ray and generator are untouched, so its next find returns the same candidate
+        // and its shade() draws the same numbers, one iteration later (the argument of §4.25). By (b) a parked hit
+        // lane has no pending sphere, so its re-find is find_pre and find_rest, which run for the other lanes anyway.
+        // Progress: shade_age counts the iterations since the first hit lane parked and is reset only by a hit
+        // trip, which shades every hit lane of the wave; a parked hit lane is a hit lane again next iteration
+        // (same candidate), so by (d) no lane waits more than RT4_DEFER_SHADE_WAIT iterations, and by (c) a wave
+        // with only hit lanes left never waits. A lane parked for its exact tests above is not a hit lane (it has
+        // no candidate yet): it leaves that park by defer_age / run alone, bounded by RT4_DEFER_WAIT, and only
+        // then meets this rule; the two ages never read or reset one another.
+        const bool hitl = active && !parked && c.hit;
+        const unsigned long long hm = __ballot(hitl);
+        const bool trip = uni(static_cast<unsigned>(__popcll(hm))) >= static_cast<unsigned>(RT4_DEFER_SHADE) ||
+                          (run && (hm & pm) != 0ull) || hm == __ballot(active && !parked) ||
+                          shade_age >= RT4_DEFER_SHADE_WAIT;
+        if (hm != 0ull && !trip) {
+          parked = parked || hitl;
+          ++shade_age;
+        } else {
+          shade_age = 0;
+        }
+      }
+#ifdef RT4_LANESTATS  // diagnostic: hit-path trips by their lanes, 1-4, 5-8, 9-16, 17-32, 33-48, 49-64, split by
+                      // whether a hit lane came through an exact test this iteration (counter[80 + 6 x + bucket]
+                      // trips, counter[92 + 6 x + bucket] lanes; x = 1: with an exact test; tools/lanestats.py)
+      {
+        const unsigned long long hm_ = __ballot(active && !parked && c.hit);
+        if (hm_ && counter && lane == static_cast<unsigned>(__builtin_ctzll(__builtin_amdgcn_read_exec()))) {
+          const unsigned n_ = static_cast<unsigned>(__popcll(hm_));
+          const unsigned bk_ = n_ <= 4u ? 0u : (n_ <= 8u ? 1u : (n_ <= 16u ? 2u : (n_ <= 32u ? 3u : (n_ <= 48u ? 4u : 5u))));
+          const unsigned x_ = run && (hm_ & pm) != 0ull ? 6u : 0u;
+          atomicAdd(counter + 80 + x_ + bk_, 1ull);
+          atomicAdd(counter + 92 + x_ + bk_, static_cast<unsigned long long>(n_));
+        }
+      }
+#endif
       RT4_ACC(1, t_ph);
     } else {
       if (!__any(active)) {

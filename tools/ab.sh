@@ -46,7 +46,7 @@ build)
       make -C "$ROOT/4d_ray_tracing_amd/csrc" -s OUT="$tmp" EXTRA="$flags" "$tmp/librt4.so" > /dev/null || return 1
       cp "$tmp/librt4.so" "$VDIR/$name.so"
     else
-      git -C "$ROOT" archive "$rev" 4d_ray_tracing_amd/csrc include | tar -x -C "$tmp"
+      git -C "$ROOT" archive "$rev" 4d_ray_tracing_amd/csrc include tools | tar -x -C "$tmp"
       make -C "$tmp/4d_ray_tracing_amd/csrc" -s OUT="$tmp/lib" "$tmp/lib/librt4.so" > /dev/null || return 1
       cp "$tmp/lib/librt4.so" "$VDIR/$name.so"
     fi

@@ -4,7 +4,7 @@
 Usage: RT4_LIB=<lanestats .so> python tools/lanestats.py [scene] [spp] [bounces] [W] [H] [frames] [mode]
   mode: "pipelined" (frames in one rt4_render_frames_device call) or "fbf" (one launch per frame).
 The counters accumulate over every launch of the run (counter[16..] per phase, counter[40..41] exact
-sphere trips, counter[60..71] tiger tests)."""
+sphere trips, counter[60..71] tiger tests, counter[80..103] hit-path trips by their lanes)."""
 import importlib
 import os
 import sys
@@ -25,7 +25,7 @@ mode = a[6] if len(a) > 6 else "fbf"
 t = rt4.Tracer(0, rt4.FLAG_SAMPLER_LUT | int(os.environ.get("RT4_EXTRA_FLAGS", "0"), 0), rt4.Scene.named(scene))
 u = rt4.make_uniforms(W, H, samples=spp, reflections=bounces, seed=12345)
 frame = torch.zeros((H, W, 4), device="cuda")
-cnt = torch.zeros(80, dtype=torch.int64, device="cuda")
+cnt = torch.zeros(104, dtype=torch.int64, device="cuda")
 s = torch.cuda.current_stream().cuda_stream
 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 if mode == "pipelined" and frames > 1:
@@ -69,4 +69,22 @@ if any(c[42:49]):
     for k, lab in enumerate(["1", "2", "3-4", "5-8", "9-16", "17-32", "33-64"]):
         if c[42 + k]:
             print(f"    {lab:>6s}: {c[42 + k] / tot:6.3f}  {c[50 + k] / c[42 + k]:5.1f}")
+if any(c[80:92]):
+    # the deferred-sphere kernels: one event per wave iteration that runs shade()'s hit path (a trip), by the lanes
+    # it runs on; "exact": a hit lane of the trip came through an exact sphere test in that iteration
+    trips, lanes = sum(c[80:92]), sum(c[92:104])
+    print(f"  hit-path trips: {trips} ({trips / max(c[16], 1):5.3f} per iteration), {lanes / trips:5.1f} lanes avg; "
+          "by lanes (share of trips, share of lane-work, lanes avg, share of the bucket's trips with an exact test):")
+    for k, lab in enumerate(["1-4", "5-8", "9-16", "17-32", "33-48", "49-64"]):
+        e, l = c[80 + k] + c[86 + k], c[92 + k] + c[98 + k]
+        if e:
+            print(f"    {lab:>6s}: {e / trips:6.3f}  {l / lanes:6.3f}  {l / e:5.1f}  {c[86 + k] / e:6.3f}")
+    cum_e = cum_l = cum_ne = cum_nl = 0
+    for k, lab in enumerate(["<= 4", "<= 8", "<= 16", "<= 32"]):
+        cum_e += c[80 + k] + c[86 + k]
+        cum_l += c[92 + k] + c[98 + k]
+        cum_ne += c[80 + k]
+        cum_nl += c[92 + k]
+        print(f"    trips of {lab:>5s} lanes: {cum_e / trips:6.3f} of trips, {cum_l / lanes:6.3f} of lane-work; "
+              f"without an exact test {cum_ne / trips:6.3f} / {cum_nl / lanes:6.3f}")
 print(f"  iterations per intersection: {c[16] / max(c[0], 1):.4f}")
