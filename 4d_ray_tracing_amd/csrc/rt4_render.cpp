@@ -27,6 +27,13 @@
 //                   accumulated image survives --keys / --move-seconds instead of restarting; the images written are
 //                   the temporal images, --denoise filters them with the temporal G-buffer. A resting camera gives the
 //                   image of a run without the flag. Not with --gpus, --resume, --checkpoint, --frame-by-frame)
+//                   [--window [SCALE]] [--window-nearest]  (next to every image also <name>_win.<ext>: the image at
+//                   window resolution, what the reference's renderWindow.draw(sprite) shows: cells * SCALE pixels,
+//                   SCALE = the window's cell_size from the properties unless given (main for YXZ, additional for the
+//                   other two). Interpolated along the primary hits of the window's pixels (one rt4_window per section,
+//                   rt4_window_present_device); --window-nearest: the reference's block stretch. With --denoise the
+//                   filtered frame is upscaled, with --reproject the temporal image with the temporal G-buffer.
+//                   One GPU only: not with --gpus)
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -306,6 +313,8 @@ int main(int argc, char** argv) {
   bool png = false, rehearse = false, raw = false;
   int denoise_levels = 0;  // --denoise: 0 = off
   bool reproject = false;
+  int window_scale = 0;  // --window: 0 = off, -1 = the properties' cell_size
+  bool window_nearest = false;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -333,6 +342,17 @@ int main(int argc, char** argv) {
     else if (a == "--raw") raw = true;
     else if (a == "--rehearse") rehearse = true;
     else if (a == "--reproject") reproject = true;
+    else if (a == "--window-nearest") {
+      window_nearest = true;
+      if (window_scale == 0) window_scale = -1;
+    }
+    else if (a == "--window") {
+      window_scale = -1;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {
+        window_scale = std::atoi(argv[++i]);
+        if (window_scale < 1 || window_scale > RT4_UPSCALE_MAX_SCALE) die("--window", "SCALE must be 1..64");
+      }
+    }
     else if (a == "--denoise") {
       rt4_denoise_params dp;
       rt4_denoise_params_default(&dp);
@@ -415,6 +435,13 @@ int main(int argc, char** argv) {
   }
 
   if (gpus > 0 && denoise_levels > 0) die("--denoise", "not with --gpus: the frame is not filtered after the gather");
+  if (gpus > 0 && window_scale != 0) die("--window", "not with --gpus: the frame is not upscaled after the gather");
+  int32_t win_scale[3] = {window_scale, window_scale, window_scale};  // per section
+  if (window_scale < 0) {
+    RT4_CHECK(rt4_properties_get_int(props, "window.main.cell_size", &win_scale[0], err, sizeof err));
+    if (three) RT4_CHECK(rt4_properties_get_int(props, "window.additional.cell_size", &win_scale[1], err, sizeof err));
+    win_scale[2] = win_scale[1];
+  }
   if (gpus > 0) {  // pixel bands over GPUs 0..gpus-1, one RCCL gather (one section, resting camera)
     if (three || (keys && move_seconds > 0.0f)) die("--gpus", "needs one section and a resting camera");
     if (frames < 1 || band < 1) die("--gpus", "frames and band must be >= 1");
@@ -528,12 +555,12 @@ int main(int argc, char** argv) {
     RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(path.c_str(), host.data(), format, cw[q], ch[q], cw[q], err, sizeof err));
     if (raw) write_raw(out + "_" + names[q] + ".raw", host);
     std::printf("wrote %s (%d x %d)\n", path.c_str(), cw[q], ch[q]);
+    rt4_gbuffer_px* d_gbuf = nullptr;  // --denoise: the G-buffer of the last pose and the filtered frame
+    void* d_dn = nullptr;
     if (denoise_levels > 0 && frames >= 1) {
       // the picture to look at: the final frame filtered along the primary hits of its camera pose (one G-buffer
       // per pose and section); d_frame stays the accumulator
       const size_t npx = static_cast<size_t>(cw[q]) * ch[q];
-      rt4_gbuffer_px* d_gbuf = nullptr;
-      void* d_dn = nullptr;
       HIP_CHECK(hipMalloc(&d_gbuf, npx * sizeof(rt4_gbuffer_px)));
       HIP_CHECK(hipMalloc(&d_dn, npx * px));
       const rt4_region reg{0, 0, cw[q], ch[q], 0, 0};
@@ -551,9 +578,30 @@ int main(int argc, char** argv) {
       RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(dn_path.c_str(), dn.data(), format, cw[q], ch[q], cw[q], err, sizeof err));
       if (raw) write_raw(out + "_" + names[q] + "_dn.raw", dn);
       std::printf("wrote %s (%d x %d, %d filter levels)\n", dn_path.c_str(), cw[q], ch[q], denoise_levels);
-      (void)hipFree(d_gbuf);
-      (void)hipFree(d_dn);
     }
+    if (window_scale != 0 && frames >= 1) {
+      // what the reference's window shows: the cell image (filtered, if it was) stretched over cells * scale pixels,
+      // interpolated along the window pixels' own primary hits unless --window-nearest
+      const int32_t sc = win_scale[q], ww = cw[q] * sc, wh = ch[q] * sc;
+      rt4_window* win = nullptr;
+      RT4_CHECK(rt4_window_create(ctx, cw[q], ch[q], sc, format, &win, err, sizeof err));
+      rt4_upscale_params up;
+      rt4_upscale_params_default(&up);
+      if (window_nearest) up.mode = RT4_UPSCALE_NEAREST;
+      // a cell G-buffer of the last pose that already exists is passed on; otherwise the window renders its own
+      const rt4_gbuffer_px* d_gcells = reproject ? rt4_temporal_gbuffer(temporal[q]) : d_dn ? d_gbuf : nullptr;
+      RT4_CHECK(rt4_window_present_device(win, &last_u[q], d_dn ? d_dn : d_frame[q], cw[q], d_gcells, cw[q], &up, nullptr, err,
+                                          sizeof err));
+      std::vector<unsigned char> wimg(static_cast<size_t>(ww) * wh * px);
+      RT4_CHECK(rt4_window_read_host(win, wimg.data(), nullptr, err, sizeof err));
+      const std::string win_path = out + "_" + names[q] + "_win" + (png ? ".png" : ".ppm");
+      RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(win_path.c_str(), wimg.data(), format, ww, wh, ww, err, sizeof err));
+      if (raw) write_raw(out + "_" + names[q] + "_win.raw", wimg);
+      std::printf("wrote %s (%d x %d, scale %d, %s)\n", win_path.c_str(), ww, wh, sc, window_nearest ? "nearest" : "guided");
+      rt4_window_destroy(win);
+    }
+    if (d_gbuf) (void)hipFree(d_gbuf);
+    if (d_dn) (void)hipFree(d_dn);
     if (q == 0 && !checkpoint_path.empty()) {
       // frames_done counts camera-resting frames only: a moving camera restarts the blend (frame_number 1)
       RT4_CHECK(rt4_accum_save_key(checkpoint_path.c_str(), host.data(), format, cw[0], ch[0], cw[0],

@@ -2998,3 +2998,4 @@ int rt4_render_gbuffer_host(rt4_context* ctx, const rt4_uniforms* u, const rt4_r
 
 #include "rt4_denoise.h"
 #include "rt4_temporal.h"
+#include "rt4_upscale.h"

@@ -159,6 +159,14 @@ class ReprojectParams(Structure):  # rt4.h rt4_reproject_params
                 ("max_history", c_int32)]
 
 
+class UpscaleParams(Structure):  # rt4.h rt4_upscale_params
+    _fields_ = [("mode", c_int32), ("cos_min", c_float), ("plane_tol", c_float)]
+
+
+UPSCALE_NEAREST, UPSCALE_GUIDED = 0, 1  # rt4.h rt4_upscale_mode
+UPSCALE_MAX_SCALE = 64
+
+
 def _gbuffer_dtype():
     import numpy as np
 
@@ -273,6 +281,21 @@ def _load(path=None):
         "rt4_temporal_gbuffer": ([c_void_p], c_void_p),
         "rt4_temporal_read_host": ([c_void_p, c_void_p, c_void_p, c_void_p] + E, c_int),
         "rt4_temporal_bytes": ([c_void_p], c_uint64),
+        "rt4_upscale_params_default": ([POINTER(UpscaleParams)], None),
+        "rt4_upscale_uniforms": ([POINTER(Uniforms), c_int32, POINTER(Uniforms)], c_int),
+        "rt4_upscale_device": ([c_void_p, POINTER(Uniforms), c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                c_void_p, c_int64, c_int32, c_int32, c_int32, POINTER(UpscaleParams), c_void_p] + E, c_int),
+        "rt4_upscale_host": ([c_void_p, POINTER(Uniforms), c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                              c_void_p, c_int64, c_int32, c_int32, c_int32, POINTER(UpscaleParams)] + E, c_int),
+        "rt4_window_create": ([c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p)] + E, c_int),
+        "rt4_window_destroy": ([c_void_p], None),
+        "rt4_window_reset": ([c_void_p], None),
+        "rt4_window_present_device": ([c_void_p, POINTER(Uniforms), c_void_p, c_int64, c_void_p, c_int64,
+                                       POINTER(UpscaleParams), c_void_p] + E, c_int),
+        "rt4_window_image": ([c_void_p], c_void_p),
+        "rt4_window_gbuffer": ([c_void_p], c_void_p),
+        "rt4_window_read_host": ([c_void_p, c_void_p, c_void_p] + E, c_int),
+        "rt4_window_bytes": ([c_void_p], c_uint64),
     }
     tolerant = os.environ.get("RT4_AB_TOLERANT") == "1"  # tools/abtest.sh: older builds lack newer exports
     for name, (argtypes, restype) in sig.items():
@@ -308,7 +331,10 @@ EXPORTED = (
     "rt4_debug_final_light "
     "rt4_reproject_params_default rt4_reproject_device rt4_reproject_host rt4_temporal_blend_device rt4_temporal_create "
     "rt4_temporal_destroy rt4_temporal_reset rt4_temporal_frame_device rt4_temporal_image rt4_temporal_history "
-    "rt4_temporal_gbuffer rt4_temporal_read_host rt4_temporal_bytes"
+    "rt4_temporal_gbuffer rt4_temporal_read_host rt4_temporal_bytes "
+    "rt4_upscale_params_default rt4_upscale_uniforms rt4_upscale_device rt4_upscale_host rt4_window_create "
+    "rt4_window_destroy rt4_window_reset rt4_window_present_device rt4_window_image rt4_window_gbuffer "
+    "rt4_window_read_host rt4_window_bytes"
 ).split()
 
 if ctypes.sizeof(SceneDesc) != lib.rt4_scene_desc_size() or ctypes.sizeof(Uniforms) != lib.rt4_uniforms_size():
@@ -515,6 +541,26 @@ def reproject_params(cos_min: float | None = None, plane_tol: float | None = Non
         if v is not None:
             setattr(p, name, v)
     return p
+
+
+def upscale_params(mode: int | None = None, cos_min: float | None = None, plane_tol: float | None = None) -> UpscaleParams:
+    """rt4_upscale_params_default (UPSCALE_GUIDED, 0.9, 0.02) with the given fields replaced."""
+    p = UpscaleParams()
+    lib.rt4_upscale_params_default(byref(p))
+    for name, v in (("mode", mode), ("cos_min", cos_min), ("plane_tol", plane_tol)):
+        if v is not None:
+            setattr(p, name, v)
+    return p
+
+
+def upscale_uniforms(u_cells: Uniforms, scale: int) -> Uniforms:
+    """The uniforms of the window a cell image of `u_cells` is stretched over: resolution * scale, nothing else
+    (rt4_upscale_uniforms)."""
+    out = Uniforms()
+    st = lib.rt4_upscale_uniforms(byref(u_cells), scale, byref(out))
+    if st != 0:
+        raise RT4Error(st, f"scale {scale} outside 1..{UPSCALE_MAX_SCALE}, or a window beyond 65535 x 16383")
+    return out
 
 
 def region(w: int, h: int, x0: int = 0, y0: int = 0, band_rows: int = 0, band_step: int = 0) -> Region:
@@ -881,6 +927,44 @@ class Tracer:
             hist_out.shape[1], fmt, w, h, byref(p), err, len(err)), err)
         return acc_out, hist_out
 
+    def upscale_device(self, u_cells: Uniforms, scale: int, cells_ptr: int, cells_stride: int, gcells_ptr: int,
+                       gcells_stride: int, gwin_ptr: int, gwin_stride: int, out_ptr: int, out_stride: int, fmt: int,
+                       cells_w: int, cells_h: int, params: UpscaleParams | None = None, stream: int = 0) -> None:
+        """Asynchronous upscale of a device cell frame to the window of cells_w*scale x cells_h*scale pixels
+        (rt4_upscale_device). UPSCALE_NEAREST takes 0 for both G-buffers."""
+        p = params if params is not None else upscale_params()
+        err = _errbuf()
+        _check(self._lib.rt4_upscale_device(
+            self._h, byref(u_cells) if u_cells is not None else None, scale, c_void_p(cells_ptr or None), cells_stride,
+            c_void_p(gcells_ptr or None), gcells_stride, c_void_p(gwin_ptr or None), gwin_stride, c_void_p(out_ptr or None),
+            out_stride, fmt, cells_w, cells_h, byref(p), c_void_p(stream or None), err, len(err)), err)
+
+    def upscale_host(self, u_cells: Uniforms, scale: int, cells, gcells=None, gwin=None, params: UpscaleParams | None = None,
+                     out=None, fmt: int | None = None, cells_w: int | None = None):
+        """Synchronous upscale of host arrays: cells (h, stride, 4) of the format's dtype, G-buffers (h, stride) and
+        (h*scale, stride) of GBUFFER_DTYPE (None with UPSCALE_NEAREST); cells_w: the cell image's width when rows are
+        padded. Returns `out` (h*scale, stride >= cells_w*scale, 4) (a new array if None)."""
+        import numpy as np
+
+        if fmt is None:
+            fmt = {np.dtype("float32"): FRAME_RGBA32F, np.dtype("float16"): FRAME_RGBA16F,
+                   np.dtype("uint8"): FRAME_RGBA8}[cells.dtype]
+        ch = cells.shape[0]
+        cw = cells.shape[1] if cells_w is None else cells_w
+        if out is None:
+            out = np.zeros((ch * scale, cw * scale, 4), cells.dtype)
+        for a, dt in ((cells, np.dtype(FRAME_NUMPY[fmt])), (out, np.dtype(FRAME_NUMPY[fmt])), (gcells, GBUFFER_DTYPE),
+                      (gwin, GBUFFER_DTYPE)):
+            assert a is None or (a.dtype == dt and a.flags["C_CONTIGUOUS"])
+        p = params if params is not None else upscale_params()
+        err = _errbuf()
+        _check(self._lib.rt4_upscale_host(
+            self._h, byref(u_cells), scale, c_void_p(cells.ctypes.data), cells.shape[1],
+            c_void_p(gcells.ctypes.data) if gcells is not None else None, gcells.shape[1] if gcells is not None else 0,
+            c_void_p(gwin.ctypes.data) if gwin is not None else None, gwin.shape[1] if gwin is not None else 0,
+            c_void_p(out.ctypes.data), out.shape[1], fmt, cw, ch, byref(p), err, len(err)), err)
+        return out
+
     def temporal_blend_device(self, new_ptr: int, new_stride: int, acc_ptr: int, acc_stride: int, fmt: int, hist_ptr: int,
                               hist_stride: int, w: int, h: int, stream: int = 0) -> None:
         """Asynchronous per-pixel progressive blend of an RGBA32F sample frame into a device accumulator of `fmt`,
@@ -1023,3 +1107,68 @@ class Temporal:
     def gbuffer(self):
         """Synchronous: the G-buffer of the last frame's pose, (h, w) of GBUFFER_DTYPE."""
         return self._read(2)
+
+
+class Window:
+    """rt4_window: cell frames presented at window resolution (cells * scale). present() upscales a device cell frame
+    into the owned window image; the G-buffers it needs are rendered only when the pose changed (rt4.h
+    rt4_window_present_device). Close it before its Tracer. After Tracer.set_scene call reset()."""
+
+    def __init__(self, tracer: Tracer, cells_w: int, cells_h: int, scale: int, fmt: int = FRAME_RGBA32F):
+        self._lib = tracer._lib
+        self._tracer = tracer  # keeps the context alive
+        self.cells_w, self.cells_h, self.scale, self.fmt = cells_w, cells_h, scale, fmt
+        self.w, self.h = cells_w * scale, cells_h * scale
+        t = c_void_p()
+        err = _errbuf()
+        _check(self._lib.rt4_window_create(tracer._h, cells_w, cells_h, scale, fmt, byref(t), err, len(err)), err)
+        self._t = t
+
+    def close(self):
+        if getattr(self, "_t", None):
+            if getattr(self._tracer, "_h", None):  # a closed Tracer took the device buffers' context with it
+                self._lib.rt4_window_destroy(self._t)
+            self._t = None
+
+    __del__ = close
+
+    def reset(self) -> None:
+        self._lib.rt4_window_reset(self._t)
+
+    def present(self, u_cells: Uniforms, cells_ptr: int, cells_stride: int | None = None, gcells_ptr: int = 0,
+                gcells_stride: int | None = None, params: UpscaleParams | None = None, stream: int = 0) -> None:
+        """Asynchronous: the device cell frame at cells_ptr (the view u_cells, this window's format) into the window
+        image. gcells_ptr: the G-buffer of u_cells when the caller has one (Temporal.gbuffer_ptr()), else 0."""
+        err = _errbuf()
+        _check(self._lib.rt4_window_present_device(
+            self._t, byref(u_cells), c_void_p(cells_ptr or None), self.cells_w if cells_stride is None else cells_stride,
+            c_void_p(gcells_ptr or None), self.cells_w if gcells_stride is None else gcells_stride,
+            byref(params) if params is not None else None, c_void_p(stream or None), err, len(err)), err)
+
+    # device pointers (row stride w)
+    def image_ptr(self) -> int:
+        return int(self._lib.rt4_window_image(self._t) or 0)
+
+    def gbuffer_ptr(self) -> int:
+        return int(self._lib.rt4_window_gbuffer(self._t) or 0)
+
+    def bytes(self) -> int:
+        return int(self._lib.rt4_window_bytes(self._t))
+
+    def image(self):
+        """Synchronous: the window image on the host, (h, w, 4) of the format's dtype."""
+        import numpy as np
+
+        out = np.zeros((self.h, self.w, 4), FRAME_NUMPY[self.fmt])
+        err = _errbuf()
+        _check(self._lib.rt4_window_read_host(self._t, c_void_p(out.ctypes.data), None, err, len(err)), err)
+        return out
+
+    def gbuffer(self):
+        """Synchronous: the window G-buffer of the last guided present's pose, (h, w) of GBUFFER_DTYPE."""
+        import numpy as np
+
+        out = np.zeros((self.h, self.w), GBUFFER_DTYPE)
+        err = _errbuf()
+        _check(self._lib.rt4_window_read_host(self._t, None, c_void_p(out.ctypes.data), err, len(err)), err)
+        return out

@@ -643,6 +643,88 @@ int rt4_temporal_read_host(rt4_temporal* t, void* image, int32_t* history, rt4_g
 /* Device bytes the object owns. */
 uint64_t rt4_temporal_bytes(const rt4_temporal* t);
 
+/* ---- window-resolution output (the reference's sprite stretch, windows.cpp:25-33) ------------
+ * The reference traces width / cell_size cells per row and stretches that texture over the window, so every cell
+ * becomes a cell_size x cell_size block (RT4_UPSCALE_NEAREST). RT4_UPSCALE_GUIDED interpolates the cell colours
+ * instead, for every window pixel only among the cells that lie on the pixel's own surface: the primary hit of a
+ * window pixel (the G-buffer of the window's uniforms) is exact and cheap, so object edges come out at window
+ * resolution. scale = cell_size; the window is W = cells_w*scale by H = cells_h*scale. G_cells is the G-buffer of
+ * u_cells, G_win the G-buffer of u_window = rt4_upscale_uniforms(u_cells, scale).
+ * Definition (fp32 round-to-nearest, no contraction, division and sqrt correctly rounded; dot is the fma chain of
+ * DESIGN.md §3, mad(a,s,b) one fma per component; the kernel matches it bit for bit). For window pixel (x, y):
+ * g = G_win(x, y), s = scale, cx = x / s, cy = y / s (integer division).
+ *   1. NEAREST: the output pixel is the stored bits of cell (cx, cy), alpha included.
+ *   2. GUIDED, the tap position (x shown, y alike): tx = 2*(x % s) + 1 - s; tx < 0: x0 = cx - 1, nx = tx + 2*s;
+ *      otherwise x0 = cx, nx = tx; ax = (float)nx / (float)(2*s), one division (floor and frac of
+ *      (x + 0.5)/s - 0.5 without rounding).
+ *   3. X = mad(d, g.depth, focus), d the primary direction of (x, y) under u_window, op for op as
+ *      rt4_render_gbuffer_device builds it; tol = plane_tol * fabsf(g.depth).
+ *   4. Taps ty = 0,1 (outer), tx = 0,1 (inner): q = (x0+tx, y0+ty), k = (tx ? ax : 1-ax) * (ty ? ay : 1-ay). A tap
+ *      counts iff q is inside the cell image, k > 0, G_cells(q).surface == g.surface and, when g.surface >= 0,
+ *      dot(n_p, n_q) >= cos_min and fabsf(dot(n_p, X_q - X)) <= tol, where X_q = mad(d_q, z_q, focus), d_q the
+ *      primary direction of cell q under u_cells and z_q = G_cells(q).depth. Comparisons with NaN are false: a hit
+ *      with a non-finite depth has no counted tap. Two misses match with no further test (the sky interpolates among
+ *      sky cells). A counted tap adds acc_c = acc_c + k * C(q)_c (a multiply, then an add; C decoded as in the
+ *      filter) and wsum = wsum + k.
+ *   5. wsum > 0: the colour acc / wsum in the frame's format (fma(c, 1, 0), then half: round to nearest even; RGBA8:
+ *      the rule of rt4_frame_format) with alpha 1. Otherwise the stored bits of cell (cx, cy), as in NEAREST.
+ * No reflectance threshold: a mirror's content is interpolated inside the mirror, only its outline is sharpened. */
+enum rt4_upscale_mode { RT4_UPSCALE_NEAREST = 0, RT4_UPSCALE_GUIDED = 1 };
+#define RT4_UPSCALE_MAX_SCALE 64
+typedef struct rt4_upscale_params {
+  int32_t mode;    /* rt4_upscale_mode */
+  float cos_min;   /* smallest dot(n_p, n_q) a tap may have */
+  float plane_tol; /* largest distance of the cell's hit point from the pixel's tangent plane, as a fraction of |depth| */
+} rt4_upscale_params;
+/* GUIDED, 0.9f, 0.02f. Starting points: nothing has been measured behind these values. */
+void rt4_upscale_params_default(rt4_upscale_params* p);
+/* *u_window = *u_cells with resolution multiplied by scale (exact integers in fp32); nothing else changes.
+ * RT4_ERR_ARG for a NULL pointer, a scale outside 1..RT4_UPSCALE_MAX_SCALE, or a window wider than 65535 or taller
+ * than 16383. */
+int rt4_upscale_uniforms(const rt4_uniforms* u_cells, int32_t scale, rt4_uniforms* u_window);
+/* d_cells: the cell frame (cells_w x cells_h, `format`); d_gcells: the G-buffer of u_cells; d_gwin: the G-buffer of
+ * the window's uniforms (W x H); d_out: W x H in `format`. Strides in elements of their image. RT4_ERR_ARG, nothing
+ * written, for a NULL pointer, an unknown format or mode, a scale outside 1..RT4_UPSCALE_MAX_SCALE, a resolution of
+ * u_cells other than (cells_w, cells_h), a stride below its image's width, a misaligned pointer (G-buffers 16 B,
+ * frames their pixel size) or an output that overlaps an input. NEAREST ignores, and accepts NULL for, both
+ * G-buffers. Asynchronous on `stream`, no allocation. Ordered with the context's other launches. */
+int rt4_upscale_device(rt4_context* ctx, const rt4_uniforms* u_cells, int32_t scale, const void* d_cells,
+                       int64_t cells_stride, const rt4_gbuffer_px* d_gcells, int64_t gcells_stride,
+                       const rt4_gbuffer_px* d_gwin, int64_t gwin_stride, void* d_out, int64_t out_stride, int32_t format,
+                       int32_t cells_w, int32_t cells_h, const rt4_upscale_params* params, void* stream, char* err,
+                       size_t errlen);
+/* The same on host buffers (synchronous; output bytes outside the window keep their values). */
+int rt4_upscale_host(rt4_context* ctx, const rt4_uniforms* u_cells, int32_t scale, const void* cells, int64_t cells_stride,
+                     const rt4_gbuffer_px* gcells, int64_t gcells_stride, const rt4_gbuffer_px* gwin, int64_t gwin_stride,
+                     void* out, int64_t out_stride, int32_t format, int32_t cells_w, int32_t cells_h,
+                     const rt4_upscale_params* params, char* err, size_t errlen);
+
+/* The state a frame loop needs to present cell frames at window resolution: the window image in `format`, the window
+ * G-buffer, a cell G-buffer and the last present's uniforms, all allocated at creation (rt4_window_bytes). Destroy it
+ * before its context. After rt4_context_set_scene call rt4_window_reset. */
+typedef struct rt4_window rt4_window;
+int rt4_window_create(rt4_context* ctx, int32_t cells_w, int32_t cells_h, int32_t scale, int32_t format, rt4_window** out,
+                      char* err, size_t errlen);
+void rt4_window_destroy(rt4_window* win); /* waits for the context's launches in flight */
+/* The next present renders its G-buffers anew, as the first present after creation does. */
+void rt4_window_reset(rt4_window* win);
+/* Upscales the cell frame d_cells (cells_w x cells_h, `format`, stride in pixels) of the view u_cells into the window
+ * image. GUIDED renders the window G-buffer, and the owned cell G-buffer when d_gcells is NULL, only when the pose of
+ * u_cells (the bytes of resolution, mtr_sizes, focus, vec_to_mtr, top_drct, right_drct) differs from the last
+ * present's or this is the first present after create / reset: a resting camera pays for the upscale alone. NEAREST
+ * renders no G-buffer. d_gcells, when given, is the G-buffer of u_cells (rt4_temporal_gbuffer, or the one passed to
+ * rt4_denoise_device). params NULL = the defaults. Asynchronous on `stream`: no allocation, no synchronisation. */
+int rt4_window_present_device(rt4_window* win, const rt4_uniforms* u_cells, const void* d_cells, int64_t cells_stride,
+                              const rt4_gbuffer_px* d_gcells, int64_t gcells_stride, const rt4_upscale_params* params,
+                              void* stream, char* err, size_t errlen);
+/* Device pointers of the window image (W x H, `format`, row stride W) and of the window G-buffer (row stride W). */
+void* rt4_window_image(const rt4_window* win);
+const rt4_gbuffer_px* rt4_window_gbuffer(const rt4_window* win);
+/* The two copied to host buffers of W x H elements (either may be NULL). Synchronous: waits for the context's launches. */
+int rt4_window_read_host(rt4_window* win, void* image, rt4_gbuffer_px* gbuf, char* err, size_t errlen);
+/* Device bytes the object owns. */
+uint64_t rt4_window_bytes(const rt4_window* win);
+
 /* ---- diagnostics (used by the parity tests; not on the render path) ------------------------- */
 /* Bytes of the context's frame-colour scratch for pipelined frames (0 before any pipelined launch or
  * reservation; a scene that runs frame by frame never allocates it). */
