@@ -34,6 +34,13 @@
 //                   rt4_window_present_device); --window-nearest: the reference's block stretch. With --denoise the
 //                   filtered frame is upscaled, with --reproject the temporal image with the temporal G-buffer.
 //                   One GPU only: not with --gpus)
+//                   [--light [--noise-threshold Q] [--noise-map]]  (light-domain accumulation, a resting camera: the -n
+//                   frames of every section go through rt4_render_light_device into a light accumulator and the image
+//                   written is its resolve, rt4_light_resolve_device; the rt4_noise_stats of every section are printed
+//                   at the end, for the threshold Q in display units (default 1/255, one 8-bit step); --noise-map: also
+//                   <prefix>_<section>_q.<ext>, the display error q as grey. An error estimate, not a stop rule: on
+//                   scenes lit by small emitters `above` rises over the first hundred frames. --denoise and --window
+//                   work on the resolved image. Not with --reproject, --resume, --checkpoint, --gpus, --frame-by-frame)
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -44,6 +51,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -315,6 +323,8 @@ int main(int argc, char** argv) {
   bool reproject = false;
   int window_scale = 0;  // --window: 0 = off, -1 = the properties' cell_size
   bool window_nearest = false;
+  bool light = false, noise_map = false;  // --light, --noise-map
+  float noise_threshold = 1.0f / 255.0f;  // --noise-threshold: one 8-bit step
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -342,6 +352,9 @@ int main(int argc, char** argv) {
     else if (a == "--raw") raw = true;
     else if (a == "--rehearse") rehearse = true;
     else if (a == "--reproject") reproject = true;
+    else if (a == "--light") light = true;
+    else if (a == "--noise-map") noise_map = true;
+    else if (a == "--noise-threshold") noise_threshold = static_cast<float>(std::atof(next()));
     else if (a == "--window-nearest") {
       window_nearest = true;
       if (window_scale == 0) window_scale = -1;
@@ -366,6 +379,13 @@ int main(int argc, char** argv) {
   if (reproject && (!resume_path.empty() || !checkpoint_path.empty()))
     die("--reproject", "not with --resume / --checkpoint: a checkpoint holds no per-pixel history");
   if (reproject && frame_by_frame) die("--reproject", "not with --frame-by-frame: every temporal frame is a launch of its own");
+  if (light && reproject) die("--light", "not with --reproject: the temporal history is a colour average");
+  if (light && (!resume_path.empty() || !checkpoint_path.empty()))
+    die("--light", "not with --resume / --checkpoint: a checkpoint holds colours, not a light accumulator");
+  if (light && gpus > 0) die("--light", "not with --gpus: the light accumulator is not gathered");
+  if (light && frame_by_frame) die("--light", "not with --frame-by-frame: the frames go through rt4_render_light_device");
+  if (light && keys && move_seconds > 0.0f) die("--light", "needs a resting camera: the accumulator averages one view");
+  if ((noise_map || noise_threshold != 1.0f / 255.0f) && !light) die("--noise-map / --noise-threshold", "need --light");
   const int32_t format = fmt_name == "f16" ? RT4_FRAME_RGBA16F : fmt_name == "rgba8" ? RT4_FRAME_RGBA8 : RT4_FRAME_RGBA32F;
   char err[1024] = {0};
   rt4_properties* props = nullptr;
@@ -496,7 +516,7 @@ int main(int argc, char** argv) {
 
   // One section and a resting camera (progressive accumulation): the frames go to the library in one
   // rt4_render_frames_device call (pipelined through one pixel queue; the same final image).
-  const bool pipelined = n_img == 1 && !(keys && move_seconds > 0.0f) && !frame_by_frame && !reproject;
+  const bool pipelined = n_img == 1 && !(keys && move_seconds > 0.0f) && !frame_by_frame && !reproject && !light;
   rt4_temporal* temporal[3] = {nullptr, nullptr, nullptr};  // --reproject: one per section
   for (int q = 0; q < n_img && reproject; q++)
     RT4_CHECK(rt4_temporal_create(ctx, cw[q], ch[q], format, &temporal[q], err, sizeof err));
@@ -515,13 +535,36 @@ int main(int argc, char** argv) {
   }
   rt4_uniforms last_u[3];  // the last frame's uniforms of every section: the camera pose the images show
   if (pipelined && !us.empty()) last_u[0] = us.back();
+  rt4_light_px* d_light[3] = {nullptr, nullptr, nullptr};  // --light: one accumulator per section
+  for (int q = 0; q < n_img && light; q++) {
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_light[q]), static_cast<size_t>(cw[q]) * ch[q] * sizeof(rt4_light_px)));
+    HIP_CHECK(hipMemset(d_light[q], 0, static_cast<size_t>(cw[q]) * ch[q] * sizeof(rt4_light_px)));  // empty
+  }
   HIP_CHECK(hipEventRecord(e0, nullptr));
+  if (light && frames >= 1) {
+    // every section's frames in one rt4_render_light_device call (frame n of every section has the same seed, as in
+    // the loop below), then the image: the accumulator resolved into the section's frame
+    const uint32_t frame_number = cam.frame_number;
+    for (int q = 0; q < n_img; q++) {
+      std::vector<rt4_uniforms> lus(static_cast<size_t>(frames));
+      cam.frame_number = frame_number;
+      for (int n = 1; n <= frames; n++)
+        RT4_CHECK(rt4_camera_frame_uniforms(&cam, &base[q], sections[q],
+                                            static_cast<int32_t>(seed ^ (static_cast<uint32_t>(n) * 0x9E3779B9u)),
+                                            &lus[static_cast<size_t>(n - 1)]));
+      last_u[q] = lus.back();
+      const rt4_region reg{0, 0, cw[q], ch[q], 0, 0};
+      RT4_CHECK(rt4_render_light_device(ctx, lus.data(), frames, &reg, d_light[q], cw[q], d_count, nullptr, err, sizeof err));
+      RT4_CHECK(rt4_light_resolve_device(ctx, d_light[q], cw[q], base[q].light_to_color_conversion_coefficient, d_frame[q],
+                                         format, cw[q], cw[q], ch[q], nullptr, err, sizeof err));
+    }
+  }
   if (pipelined) {
     const rt4_region reg{0, 0, cw[0], ch[0], 0, 0};
     RT4_CHECK(rt4_render_frames_device(ctx, us.data(), frames, &reg, d_frame[0], format, cw[0], d_count, nullptr, err,
                                        sizeof err));
   }
-  for (int n = 1; n <= frames && !pipelined; n++) {
+  for (int n = 1; n <= frames && !pipelined && !light; n++) {
     const int32_t s_n = static_cast<int32_t>(seed ^ (static_cast<uint32_t>(frames_done + n) * 0x9E3779B9u));
     rt4_section_job jobs[3];
     const uint32_t frame_number = cam.frame_number;
@@ -602,6 +645,38 @@ int main(int argc, char** argv) {
     }
     if (d_gbuf) (void)hipFree(d_gbuf);
     if (d_dn) (void)hipFree(d_dn);
+    if (light) {
+      // the error estimate of the section: its statistics and, with --noise-map, the display error q as grey
+      const size_t npx = static_cast<size_t>(cw[q]) * ch[q];
+      float* d_q = nullptr;
+      rt4_noise_stats* d_stats = nullptr;
+      if (noise_map) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_q), npx * sizeof(float)));
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_stats), sizeof(rt4_noise_stats)));
+      RT4_CHECK(rt4_light_noise_device(ctx, d_light[q], cw[q], cw[q], ch[q], base[q].light_to_color_conversion_coefficient,
+                                       noise_threshold, nullptr, d_q, cw[q], nullptr, d_stats, nullptr, err, sizeof err));
+      HIP_CHECK(hipDeviceSynchronize());
+      rt4_noise_stats ns;
+      HIP_CHECK(hipMemcpy(&ns, d_stats, sizeof ns, hipMemcpyDeviceToHost));
+      if (noise_map) {
+        std::vector<float> qv(npx), grey(npx * 4);
+        HIP_CHECK(hipMemcpy(qv.data(), d_q, npx * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t p = 0; p < npx; p++) {  // the writers clamp to [0, 1]: an unmeasured pixel (+inf) is white; NaN black
+          const float v = std::isnan(qv[p]) ? 0.0f : qv[p];
+          grey[4 * p] = grey[4 * p + 1] = grey[4 * p + 2] = v;
+          grey[4 * p + 3] = 1.0f;
+        }
+        const std::string q_path = out + "_" + names[q] + "_q" + (png ? ".png" : ".ppm");
+        RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(q_path.c_str(), grey.data(), RT4_FRAME_RGBA32F, cw[q], ch[q], cw[q], err,
+                                                        sizeof err));
+        std::printf("wrote %s (%d x %d, display error q)\n", q_path.c_str(), cw[q], ch[q]);
+        (void)hipFree(d_q);
+      }
+      (void)hipFree(d_stats);
+      std::printf("noise %s: pixels %llu, measured %llu, above %llu (threshold %.6g), max_q %.6g, max_se %.6g\n", names[q],
+                  static_cast<unsigned long long>(ns.pixels), static_cast<unsigned long long>(ns.measured),
+                  static_cast<unsigned long long>(ns.above), static_cast<double>(noise_threshold),
+                  static_cast<double>(ns.max_q), static_cast<double>(ns.max_se));
+    }
     if (q == 0 && !checkpoint_path.empty()) {
       // frames_done counts camera-resting frames only: a moving camera restarts the blend (frame_number 1)
       RT4_CHECK(rt4_accum_save_key(checkpoint_path.c_str(), host.data(), format, cw[0], ch[0], cw[0],
@@ -613,6 +688,8 @@ int main(int argc, char** argv) {
               count, ms / frames, static_cast<double>(count) / (ms * 1e-3));
 
   for (int q = 0; q < n_img; q++) rt4_temporal_destroy(temporal[q]);
+  for (int q = 0; q < n_img; q++)
+    if (d_light[q]) (void)hipFree(d_light[q]);
   for (int q = 0; q < n_img; q++) (void)hipFree(d_frame[q]);
   (void)hipFree(d_count);
   rt4_context_destroy(ctx);

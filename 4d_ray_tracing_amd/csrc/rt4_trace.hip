@@ -2248,6 +2248,15 @@ struct FramePlan {
   const float* parts;
 };
 
+// A launch into a light accumulator (rt4_render_light_device, rt4_light.h): its frames' light sums go to the
+// frame-colour scratch whatever their number, and rt4_fold_light_kernel folds them in place of rt4_fold_frames_kernel.
+struct LightTarget {
+  rt4_light_px* light;
+  int64_t row_stride_px;
+};
+__global__ __launch_bounds__(256) void rt4_fold_light_kernel(const KernelArgs a, rt4_light_px* light, int64_t light_stride,
+                                      unsigned long long* count_src, unsigned long long* count_dst);
+
 // The trace kernel a launch of the context runs: its scene's shape, the sampler table, primary reuse.
 TraceFn trace_fn_of(const rt4_context* ctx) {
   const bool reuse = (ctx->flags & RT4_FLAG_PRIMARY_REUSE) && ctx->shape != GENERIC;
@@ -2294,7 +2303,8 @@ int ensure_overlap_buffer(rt4_context* ctx, unsigned k, size_t need, char* err, 
 }
 
 int launch_jobs(rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, int32_t format,
-                unsigned long long* d_counter, void* stream, char* err, size_t errlen, const FramePlan* fp = nullptr) {
+                unsigned long long* d_counter, void* stream, char* err, size_t errlen, const FramePlan* fp = nullptr,
+                const LightTarget* lt = nullptr) {
   if (!ctx || !jobs) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
   if (!ctx->has_scene) return rt4_set_err(err, errlen, "context has no scene (rt4_context_set_scene)"), RT4_ERR_ARG;
   if (n_jobs < 1 || n_jobs > RT4_MAX_SECTIONS)
@@ -2340,7 +2350,7 @@ int launch_jobs(rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, i
   if (tiles == 0) return RT4_OK;
   a.total = tiles * 64u;
   a.n_frames = 1;
-  const bool frames = fp && fp->n > 1;
+  const bool frames = fp && (fp->n > 1 || lt);  // a light launch of one frame goes through the scratch too
   if (frames) {
     if (n_jobs != 1 || fp->n > RT4_MAX_FRAMES || a.jobs[0].reg.w > 8191 || a.jobs[0].reg.h > 8191 ||
         static_cast<uint64_t>(tiles) * 64u * static_cast<uint64_t>(fp->n) >= (1ull << 31))
@@ -2499,9 +2509,13 @@ int launch_jobs(rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, i
   if (le == hipSuccess && (frames || overlap)) {
     long long npx = 0;  // the largest image's pixels (blockIdx.y: the section)
     for (int q = 0; q < n_jobs; q++) npx = std::max(npx, static_cast<long long>(a.jobs[q].reg.w) * a.jobs[q].reg.h);
-    hipLaunchKernelGGL(rt4_fold_frames_kernel, dim3(static_cast<unsigned>((npx + 255) / 256), static_cast<unsigned>(n_jobs)),
-                       dim3(256), 0, s, a,
-                       overlap ? count : nullptr, overlap ? d_counter : nullptr);
+    if (lt) {  // the light accumulator's fold in place of the colour fold (rt4_light.h)
+      hipLaunchKernelGGL(rt4_fold_light_kernel, dim3(static_cast<unsigned>((npx + 255) / 256)), dim3(256), 0, s, a, lt->light,
+                         lt->row_stride_px, overlap ? count : nullptr, overlap ? d_counter : nullptr);
+    } else {
+      hipLaunchKernelGGL(rt4_fold_frames_kernel, dim3(static_cast<unsigned>((npx + 255) / 256), static_cast<unsigned>(n_jobs)),
+                         dim3(256), 0, s, a, overlap ? count : nullptr, overlap ? d_counter : nullptr);
+    }
     le = hipGetLastError();
   }
   // Record the events whatever happened: a launch that may have been enqueued still orders the next
@@ -2999,3 +3013,4 @@ int rt4_render_gbuffer_host(rt4_context* ctx, const rt4_uniforms* u, const rt4_r
 #include "rt4_denoise.h"
 #include "rt4_temporal.h"
 #include "rt4_upscale.h"
+#include "rt4_light.h"

@@ -165,6 +165,15 @@ class UpscaleParams(Structure):  # rt4.h rt4_upscale_params
 
 UPSCALE_NEAREST, UPSCALE_GUIDED = 0, 1  # rt4.h rt4_upscale_mode
 UPSCALE_MAX_SCALE = 64
+MAX_FRAMES = 64  # rt4.h RT4_MAX_FRAMES
+
+
+class LightPx(Structure):  # rt4.h rt4_light_px: one pixel of a light accumulator
+    _fields_ = [("mean", F3), ("mean_y", c_float), ("m2", c_float), ("n", c_int32), ("reserved", F2)]
+
+
+class NoiseStats(Structure):  # rt4.h rt4_noise_stats
+    _fields_ = [("pixels", c_uint64), ("measured", c_uint64), ("above", c_uint64), ("max_q", c_float), ("max_se", c_float)]
 
 
 def _gbuffer_dtype():
@@ -175,6 +184,16 @@ def _gbuffer_dtype():
 
 # numpy layout of rt4_gbuffer_px (32 B): arrays of shape (h, stride) for Tracer.render_gbuffer_host / denoise_host
 GBUFFER_DTYPE = _gbuffer_dtype()
+
+
+def _light_dtype():
+    import numpy as np
+
+    return np.dtype([("mean", "<f4", (3,)), ("mean_y", "<f4"), ("m2", "<f4"), ("n", "<i4"), ("reserved", "<f4", (2,))])
+
+
+# numpy layout of rt4_light_px (32 B): arrays of shape (h, stride); np.zeros is the empty accumulator
+LIGHT_DTYPE = _light_dtype()
 
 
 def _load(path=None):
@@ -296,6 +315,18 @@ def _load(path=None):
         "rt4_window_gbuffer": ([c_void_p], c_void_p),
         "rt4_window_read_host": ([c_void_p, c_void_p, c_void_p] + E, c_int),
         "rt4_window_bytes": ([c_void_p], c_uint64),
+        "rt4_render_light_device": ([c_void_p, POINTER(Uniforms), c_int32, POINTER(Region), c_void_p, c_int64, c_void_p,
+                                     c_void_p] + E, c_int),
+        "rt4_render_light_host": ([c_void_p, POINTER(Uniforms), c_int32, POINTER(Region), c_void_p, c_int64,
+                                   POINTER(c_uint64)] + E, c_int),
+        "rt4_light_resolve_device": ([c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int32, c_int64, c_int32, c_int32,
+                                      c_void_p] + E, c_int),
+        "rt4_light_resolve_host": ([c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int32, c_int64, c_int32, c_int32] + E,
+                                   c_int),
+        "rt4_light_noise_device": ([c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p,
+                                    c_int64, c_void_p, c_void_p, c_void_p] + E, c_int),
+        "rt4_light_noise_host": ([c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p,
+                                  c_int64, c_void_p, POINTER(NoiseStats)] + E, c_int),
     }
     tolerant = os.environ.get("RT4_AB_TOLERANT") == "1"  # tools/abtest.sh: older builds lack newer exports
     for name, (argtypes, restype) in sig.items():
@@ -334,7 +365,9 @@ EXPORTED = (
     "rt4_temporal_gbuffer rt4_temporal_read_host rt4_temporal_bytes "
     "rt4_upscale_params_default rt4_upscale_uniforms rt4_upscale_device rt4_upscale_host rt4_window_create "
     "rt4_window_destroy rt4_window_reset rt4_window_present_device rt4_window_image rt4_window_gbuffer "
-    "rt4_window_read_host rt4_window_bytes"
+    "rt4_window_read_host rt4_window_bytes "
+    "rt4_render_light_device rt4_render_light_host rt4_light_resolve_device rt4_light_resolve_host "
+    "rt4_light_noise_device rt4_light_noise_host"
 ).split()
 
 if ctypes.sizeof(SceneDesc) != lib.rt4_scene_desc_size() or ctypes.sizeof(Uniforms) != lib.rt4_uniforms_size():
@@ -973,6 +1006,92 @@ class Tracer:
         _check(self._lib.rt4_temporal_blend_device(self._h, c_void_p(new_ptr or None), new_stride, c_void_p(acc_ptr or None),
                                                    acc_stride, fmt, c_void_p(hist_ptr or None), hist_stride, w, h,
                                                    c_void_p(stream or None), err, len(err)), err)
+
+    def render_light_device(self, us, reg: Region, light_ptr: int, row_stride_px: int, counter_ptr: int = 0,
+                            stream: int = 0) -> None:
+        """Asynchronous: len(us) frames folded in order onto a device light accumulator (rt4_light_px, 32 B per pixel;
+        zero bytes = empty), rt4_render_light_device. us may differ only in seed and part; part is ignored."""
+        arr = (Uniforms * len(us))(*us)
+        err = _errbuf()
+        _check(self._lib.rt4_render_light_device(self._h, arr, len(us), byref(reg), c_void_p(light_ptr or None), row_stride_px,
+                                                 c_void_p(counter_ptr or None), c_void_p(stream or None), err, len(err)), err)
+
+    def render_light_host(self, us, reg: Region, light=None, row_stride_px: int | None = None):
+        """Synchronous: len(us) frames folded onto a host accumulator (h, stride) of LIGHT_DTYPE (a new, empty one if
+        None). Returns (light, intersection count)."""
+        import numpy as np
+
+        if light is None:
+            light = np.zeros((reg.h, row_stride_px or reg.w), LIGHT_DTYPE)
+        assert light.dtype == LIGHT_DTYPE and light.flags["C_CONTIGUOUS"]
+        stride = row_stride_px if row_stride_px is not None else light.shape[1]
+        arr = (Uniforms * len(us))(*us)
+        n = c_uint64()
+        err = _errbuf()
+        _check(self._lib.rt4_render_light_host(self._h, arr, len(us), byref(reg), c_void_p(light.ctypes.data), stride,
+                                               byref(n), err, len(err)), err)
+        return light, n.value
+
+    def light_resolve_device(self, light_ptr: int, light_stride: int, k: float, frame_ptr: int, fmt: int, frame_stride: int,
+                             w: int, h: int, stream: int = 0) -> None:
+        """Asynchronous: the image of a device light accumulator in `fmt`, tone-mapped with k (rt4_light_resolve_device)."""
+        err = _errbuf()
+        _check(self._lib.rt4_light_resolve_device(self._h, c_void_p(light_ptr or None), light_stride, k,
+                                                  c_void_p(frame_ptr or None), fmt, frame_stride, w, h,
+                                                  c_void_p(stream or None), err, len(err)), err)
+
+    def light_resolve_host(self, light, k: float, fmt: int = FRAME_RGBA32F, out=None, w: int | None = None):
+        """Synchronous: the image of a host accumulator (h, stride) of LIGHT_DTYPE as (h, stride >= w, 4) of the
+        format's dtype; w: the image width when rows are padded. Returns `out` (a new array if None)."""
+        import numpy as np
+
+        assert light.dtype == LIGHT_DTYPE and light.flags["C_CONTIGUOUS"]
+        h = light.shape[0]
+        w = light.shape[1] if w is None else w
+        if out is None:
+            out = np.zeros((h, w, 4), FRAME_NUMPY[fmt])
+        assert out.dtype == np.dtype(FRAME_NUMPY[fmt]) and out.flags["C_CONTIGUOUS"] and out.shape[0] == h
+        err = _errbuf()
+        _check(self._lib.rt4_light_resolve_host(self._h, c_void_p(light.ctypes.data), light.shape[1], k,
+                                                c_void_p(out.ctypes.data), fmt, out.shape[1], w, h, err, len(err)), err)
+        return out
+
+    def light_noise_device(self, light_ptr: int, light_stride: int, w: int, h: int, k: float, threshold: float,
+                           se_ptr: int, q_ptr: int, map_stride: int, tile_ptr: int, stats_ptr: int, stream: int = 0) -> None:
+        """Asynchronous: the standard-error map, the display-error map q (float, row stride map_stride), `above` per 8x8
+        tile (int32, ceil(w/8) x ceil(h/8)) and the rt4_noise_stats of a device accumulator (rt4_light_noise_device).
+        Any of se_ptr, q_ptr, tile_ptr may be 0."""
+        err = _errbuf()
+        _check(self._lib.rt4_light_noise_device(self._h, c_void_p(light_ptr or None), light_stride, w, h, k, threshold,
+                                                c_void_p(se_ptr or None), c_void_p(q_ptr or None), map_stride,
+                                                c_void_p(tile_ptr or None), c_void_p(stats_ptr or None),
+                                                c_void_p(stream or None), err, len(err)), err)
+
+    def light_noise_host(self, light, k: float, threshold: float, w: int | None = None, se=True, q=True, tiles=True):
+        """Synchronous: (se, q, tile_above, stats) of a host accumulator (h, stride) of LIGHT_DTYPE: float32 (h, w) maps,
+        the int32 (ceil(h/8), ceil(w/8)) tile image and a dict of rt4_noise_stats. se / q / tiles: True for a new array,
+        an array to write into (maps: shape (h, stride >= w), one stride for both), or False / None to leave it out."""
+        import numpy as np
+
+        assert light.dtype == LIGHT_DTYPE and light.flags["C_CONTIGUOUS"]
+        h = light.shape[0]
+        w = light.shape[1] if w is None else w
+        se = np.zeros((h, w), np.float32) if se is True else (se if se is not False else None)
+        q = np.zeros((h, w), np.float32) if q is True else (q if q is not False else None)
+        tiles = np.zeros(((h + 7) // 8, (w + 7) // 8), np.int32) if tiles is True else (tiles if tiles is not False else None)
+        maps = [m for m in (se, q) if m is not None]
+        for m in maps:
+            assert m.dtype == np.float32 and m.flags["C_CONTIGUOUS"] and m.shape[0] == h and m.shape[1] == maps[0].shape[1]
+        assert tiles is None or (tiles.dtype == np.int32 and tiles.flags["C_CONTIGUOUS"])
+        st = NoiseStats()
+        err = _errbuf()
+        _check(self._lib.rt4_light_noise_host(
+            self._h, c_void_p(light.ctypes.data), light.shape[1], w, h, k, threshold,
+            c_void_p(se.ctypes.data) if se is not None else None, c_void_p(q.ctypes.data) if q is not None else None,
+            maps[0].shape[1] if maps else w, c_void_p(tiles.ctypes.data) if tiles is not None else None, byref(st), err,
+            len(err)), err)
+        return se, q, tiles, {"pixels": st.pixels, "measured": st.measured, "above": st.above, "max_q": st.max_q,
+                              "max_se": st.max_se}
 
     @property
     def kernel_shape(self) -> int:

@@ -725,6 +725,82 @@ int rt4_window_read_host(rt4_window* win, void* image, rt4_gbuffer_px* gbuf, cha
 /* Device bytes the object owns. */
 uint64_t rt4_window_bytes(const rt4_window* win);
 
+/* ---- light-domain accumulation with a per-pixel standard error (no reference counterpart) ----
+ * Every other accumulator averages tone-mapped colours, as the reference's texture does. The tone curve
+ * 1 - 1/(k*x + 1) is concave, so that average is darker than the image the samples describe, by an amount that
+ * depends on how the samples are split into frames. This accumulator averages each frame's light (light sum /
+ * samples) and tone-maps once, when the image is resolved; the running second moment of the luminance gives a
+ * standard error per pixel for one more fma. Opt-in: the light average shows the fireflies that per-frame tone
+ * mapping clamps, so the default accumulators do not change.
+ * Definition (fp32 round-to-nearest, no contraction, division and sqrt correctly rounded, fma explicit; the kernels
+ * match it bit for bit). One frame with light sum L (what the trace kernel hands the fold) for a pixel with state s:
+ *   x_c = L_c / (float)samples (the division of the tone map); y = fma(0.2126f, x_r, fma(0.7152f, x_g, 0.0722f * x_b));
+ *   n' = n + 1 (saturating at INT32_MAX); inv = 1.0f / (float)n';
+ *   d_c = x_c - mean_c; mean_c' = fma(d_c, inv, mean_c);
+ *   dy = y - mean_y; mean_y' = fma(dy, inv, mean_y); m2' = fma(dy, y - mean_y', m2).
+ * Frames are applied in order. NaN and inf propagate as the operations give them (a NaN's payload is not defined).
+ * Resolve: c = 1.0f - 1.0f / fma(k, mean_c, 1.0f) per channel, stored through the format's rule (the blend of
+ * rt4_render_device_ex with part = 1 into a zero pixel: alpha 1); a pixel with n == 0 gets colour 0, alpha 1. After
+ * exactly one frame mean = x, so the resolved RGBA32F image equals rt4_render_device_ex with part = 1 into zeros bit
+ * for bit.
+ * Noise, for a pixel with n >= 2: se = sqrtf((m2 / (float)(n - 1)) / (float)n), the standard error of mean_y;
+ * t(v) = 1.0f - 1.0f / fma(k, v, 1.0f); q = t(mean_y + se) - t(mean_y): how far the displayed luminance moves when
+ * the mean moves up one standard error, in display units. A pixel with n < 2 is unmeasured: se = q = +inf in the
+ * maps, and it counts neither in `above` nor in the maxima.
+ * The estimate is heavy-tailed: a pixel reads se = 0 until its first bright path arrives, so on scenes lit by small
+ * emitters the share of pixels above a threshold RISES over the first hundred or so frames. It is an error map, not
+ * a convergence test: do not stop a render because `above` is 0. */
+typedef struct rt4_light_px { /* 32 B; all-zero bytes = the empty accumulator */
+  float mean[3];     /* running mean of the frame's light, light sum / samples */
+  float mean_y;      /* running mean of its luminance */
+  float m2;          /* Welford sum of squared luminance deviations */
+  int32_t n;         /* frames accumulated, saturating at INT32_MAX */
+  float reserved[2]; /* written as 0 */
+} rt4_light_px;
+
+/* Exact (integer counts, maxima): the same for every order the tiles finish in. */
+typedef struct rt4_noise_stats {
+  uint64_t pixels, measured, above; /* w * h; pixels with n >= 2; measured pixels with q > threshold (false for NaN) */
+  float max_q, max_se;              /* fmaxf over 0 and the measured pixels' values (NaN ignored); 0 when none */
+} rt4_noise_stats;
+
+/* rt4_render_frames_device into a light accumulator: n_frames frames of u[0], u[1], ... folded in order onto what
+ * d_light holds (pixel (i, j) of the region at d_light + i*row_stride_px + j, as a frame; a banded region accumulates
+ * its own pixels). A hipMemsetAsync to zero is the reset. u[f] may differ from u[0] only in seed and part, and part is
+ * ignored. d_counter counts as usual. The frames run in launches of rt4_context_frames_per_launch frames through the
+ * context's frame scratch (16 B per pixel and frame; a launch of one frame too): the first call with a larger scratch
+ * need allocates (synchronises the stream once; rt4_context_reserve_frames does it ahead of time). RT4_ERR_ARG for a
+ * region wider or taller than 8191 (the scratch's pixel word holds no more) and for a d_light that is not 16-byte
+ * aligned. Asynchronous; ordered with the context's other launches. */
+int rt4_render_light_device(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, const rt4_region* region,
+                            rt4_light_px* d_light, int64_t row_stride_px, unsigned long long* d_counter, void* stream,
+                            char* err, size_t errlen);
+/* The same onto a host accumulator (synchronous; bytes outside the region's pixels keep their values).
+ * n_intersections (may be NULL) receives the count. */
+int rt4_render_light_host(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, const rt4_region* region,
+                          rt4_light_px* light, int64_t row_stride_px, uint64_t* n_intersections, char* err, size_t errlen);
+/* The w x h image of a light accumulator in `format`, tone-mapped with k. Strides in elements of their image.
+ * RT4_ERR_ARG, nothing written, for a NULL pointer, an unknown format, w or h outside [1, 65535], a stride below w, a
+ * misaligned pointer (accumulator 16 B, frame its pixel size) or a frame that overlaps the accumulator.
+ * Asynchronous on `stream`, no allocation. Ordered with the context's other launches. */
+int rt4_light_resolve_device(rt4_context* ctx, const rt4_light_px* d_light, int64_t light_stride, float k, void* d_frame,
+                             int32_t format, int64_t frame_stride, int32_t w, int32_t h, void* stream, char* err,
+                             size_t errlen);
+int rt4_light_resolve_host(rt4_context* ctx, const rt4_light_px* light, int64_t light_stride, float k, void* frame,
+                           int32_t format, int64_t frame_stride, int32_t w, int32_t h, char* err, size_t errlen);
+/* The error maps and their statistics. d_se, d_q: float images (row stride map_stride floats); d_tile_above: int32,
+ * `above` per 8x8 tile, row-major over ceil(w/8) x ceil(h/8) tiles, no padding; any of the three may be NULL. d_stats
+ * (8-byte aligned) is written completely on every call: the call zeroes it on the stream first. RT4_ERR_ARG, nothing
+ * written, for a NULL accumulator or d_stats, w or h outside [1, 65535], a stride below w, a misaligned pointer
+ * (accumulator 16 B, maps and tiles 4 B, stats 8 B) or an output that overlaps the accumulator or another output.
+ * Asynchronous on `stream`, no allocation. Ordered with the context's other launches. */
+int rt4_light_noise_device(rt4_context* ctx, const rt4_light_px* d_light, int64_t light_stride, int32_t w, int32_t h,
+                           float k, float threshold, float* d_se, float* d_q, int64_t map_stride, int32_t* d_tile_above,
+                           rt4_noise_stats* d_stats, void* stream, char* err, size_t errlen);
+int rt4_light_noise_host(rt4_context* ctx, const rt4_light_px* light, int64_t light_stride, int32_t w, int32_t h, float k,
+                         float threshold, float* se, float* q, int64_t map_stride, int32_t* tile_above,
+                         rt4_noise_stats* stats, char* err, size_t errlen);
+
 /* ---- diagnostics (used by the parity tests; not on the render path) ------------------------- */
 /* Bytes of the context's frame-colour scratch for pipelined frames (0 before any pipelined launch or
  * reservation; a scene that runs frame by frame never allocates it). */
