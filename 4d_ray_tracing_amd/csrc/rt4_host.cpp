@@ -799,6 +799,16 @@ void rt4_denoise_params_default(rt4_denoise_params* p) {
   p->max_refl_prob = 0.5f;
 }
 
+void rt4_light_denoise_params_default(rt4_light_denoise_params* p) {
+  if (!p) return;
+  p->levels = 5;
+  p->cos_min = 0.9f;
+  p->depth_tol = 0.1f;
+  p->max_refl_prob = 0.5f;
+  p->sigma = 4.0f;
+  p->eps = 1e-6f;
+}
+
 const char* rt4_build_info(void) {
   return "rt4 0.2 " RT4_KERNEL_VERSION " target=gfx950 fp32-contract=off div/sqrt=correctly-rounded built " __DATE__;
 }

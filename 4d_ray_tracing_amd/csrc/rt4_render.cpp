@@ -41,6 +41,10 @@
 //                   <prefix>_<section>_q.<ext>, the display error q as grey. An error estimate, not a stop rule: on
 //                   scenes lit by small emitters `above` rises over the first hundred frames. --denoise and --window
 //                   work on the resolved image. Not with --reproject, --resume, --checkpoint, --gpus, --frame-by-frame)
+//                   [--light-denoise [levels]]  (needs --light: next to every image also <name>_ldn.<ext>, the light
+//                   accumulator through the variance-guided filter, rt4_render_gbuffer_device of the section's pose +
+//                   rt4_light_denoise_device, tone-mapped once at the end; with --window the filtered frame is the one
+//                   upscaled. Not with --denoise, which filters the resolved colours)
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -320,6 +324,7 @@ int main(int argc, char** argv) {
   std::string resume_path, checkpoint_path;
   bool png = false, rehearse = false, raw = false;
   int denoise_levels = 0;  // --denoise: 0 = off
+  int light_denoise_levels = -1;  // --light-denoise: -1 = off
   bool reproject = false;
   int window_scale = 0;  // --window: 0 = off, -1 = the properties' cell_size
   bool window_nearest = false;
@@ -373,6 +378,14 @@ int main(int argc, char** argv) {
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise_levels = std::atoi(argv[++i]);
       if (denoise_levels < 1 || denoise_levels > RT4_DENOISE_MAX_LEVELS) die("--denoise", "levels must be 1..6");
     }
+    else if (a == "--light-denoise") {
+      rt4_light_denoise_params lp;
+      rt4_light_denoise_params_default(&lp);
+      light_denoise_levels = lp.levels;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') light_denoise_levels = std::atoi(argv[++i]);
+      if (light_denoise_levels < 0 || light_denoise_levels > RT4_LIGHT_DENOISE_MAX_LEVELS)
+        die("--light-denoise", "levels must be 0..6");
+    }
     else die("unknown argument", a.c_str());
   }
   if (reproject && gpus > 0) die("--reproject", "not with --gpus: the temporal image lives on one GPU");
@@ -386,6 +399,9 @@ int main(int argc, char** argv) {
   if (light && frame_by_frame) die("--light", "not with --frame-by-frame: the frames go through rt4_render_light_device");
   if (light && keys && move_seconds > 0.0f) die("--light", "needs a resting camera: the accumulator averages one view");
   if ((noise_map || noise_threshold != 1.0f / 255.0f) && !light) die("--noise-map / --noise-threshold", "need --light");
+  if (light_denoise_levels >= 0 && !light) die("--light-denoise", "needs --light: it filters the light accumulator");
+  if (light_denoise_levels >= 0 && denoise_levels > 0)
+    die("--light-denoise", "not with --denoise: one filtered frame per image");
   const int32_t format = fmt_name == "f16" ? RT4_FRAME_RGBA16F : fmt_name == "rgba8" ? RT4_FRAME_RGBA8 : RT4_FRAME_RGBA32F;
   char err[1024] = {0};
   rt4_properties* props = nullptr;
@@ -621,6 +637,27 @@ int main(int argc, char** argv) {
       RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(dn_path.c_str(), dn.data(), format, cw[q], ch[q], cw[q], err, sizeof err));
       if (raw) write_raw(out + "_" + names[q] + "_dn.raw", dn);
       std::printf("wrote %s (%d x %d, %d filter levels)\n", dn_path.c_str(), cw[q], ch[q], denoise_levels);
+    }
+    if (light_denoise_levels >= 0 && frames >= 1) {
+      // --light-denoise: the section's light accumulator filtered along the primary hits of its pose, with each
+      // pixel's own standard error as the luminance tolerance, and tone-mapped once; the accumulator is only read
+      const size_t npx = static_cast<size_t>(cw[q]) * ch[q];
+      HIP_CHECK(hipMalloc(&d_gbuf, npx * sizeof(rt4_gbuffer_px)));
+      HIP_CHECK(hipMalloc(&d_dn, npx * px));
+      const rt4_region reg{0, 0, cw[q], ch[q], 0, 0};
+      rt4_light_denoise_params lp;
+      rt4_light_denoise_params_default(&lp);
+      lp.levels = light_denoise_levels;
+      RT4_CHECK(rt4_render_gbuffer_device(ctx, &last_u[q], &reg, d_gbuf, cw[q], nullptr, err, sizeof err));
+      RT4_CHECK(rt4_light_denoise_device(ctx, d_light[q], cw[q], d_gbuf, cw[q], base[q].light_to_color_conversion_coefficient,
+                                         &lp, d_dn, format, cw[q], nullptr, 0, cw[q], ch[q], nullptr, err, sizeof err));
+      HIP_CHECK(hipDeviceSynchronize());
+      std::vector<unsigned char> dn(host.size());
+      HIP_CHECK(hipMemcpy(dn.data(), d_dn, dn.size(), hipMemcpyDeviceToHost));
+      const std::string dn_path = out + "_" + names[q] + "_ldn" + (png ? ".png" : ".ppm");
+      RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(dn_path.c_str(), dn.data(), format, cw[q], ch[q], cw[q], err, sizeof err));
+      if (raw) write_raw(out + "_" + names[q] + "_ldn.raw", dn);
+      std::printf("wrote %s (%d x %d, %d light filter levels)\n", dn_path.c_str(), cw[q], ch[q], light_denoise_levels);
     }
     if (window_scale != 0 && frames >= 1) {
       // what the reference's window shows: the cell image (filtered, if it was) stretched over cells * scale pixels,

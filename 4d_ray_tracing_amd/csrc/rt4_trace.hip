@@ -1730,6 +1730,10 @@ struct rt4_context {
   // (normal 16 B, {id, depth} 8 B), 56 B per pixel of the largest frame filtered, in one allocation.
   void* d_denoise = nullptr;
   size_t denoise_px = 0;  // pixels it holds
+  // Scratch of rt4_light_denoise_device (rt4_light_denoise.h), separate from the colour filter's: two states
+  // ({L, Y} 16 B, V 4 B) and the repacked guide (24 B), 64 B per pixel of the largest image filtered, in one allocation.
+  void* d_light_denoise = nullptr;
+  size_t light_denoise_px = 0;  // pixels it holds
 };
 
 #define HIP_TRY(expr)                                                                            \
@@ -2194,6 +2198,7 @@ void rt4_context_destroy(rt4_context* ctx) {
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
   if (ctx->d_eval) (void)hipFree(ctx->d_eval);
   if (ctx->d_denoise) (void)hipFree(ctx->d_denoise);
+  if (ctx->d_light_denoise) (void)hipFree(ctx->d_light_denoise);
   delete ctx;
 }
 
@@ -3014,3 +3019,4 @@ int rt4_render_gbuffer_host(rt4_context* ctx, const rt4_uniforms* u, const rt4_r
 #include "rt4_temporal.h"
 #include "rt4_upscale.h"
 #include "rt4_light.h"
+#include "rt4_light_denoise.h"

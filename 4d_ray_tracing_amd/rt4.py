@@ -176,6 +176,14 @@ class NoiseStats(Structure):  # rt4.h rt4_noise_stats
     _fields_ = [("pixels", c_uint64), ("measured", c_uint64), ("above", c_uint64), ("max_q", c_float), ("max_se", c_float)]
 
 
+class LightDenoiseParams(Structure):  # rt4.h rt4_light_denoise_params
+    _fields_ = [("levels", c_int32), ("cos_min", c_float), ("depth_tol", c_float), ("max_refl_prob", c_float),
+                ("sigma", c_float), ("eps", c_float)]
+
+
+LIGHT_DENOISE_MAX_LEVELS = 6
+
+
 def _gbuffer_dtype():
     import numpy as np
 
@@ -327,6 +335,12 @@ def _load(path=None):
                                     c_int64, c_void_p, c_void_p, c_void_p] + E, c_int),
         "rt4_light_noise_host": ([c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p,
                                   c_int64, c_void_p, POINTER(NoiseStats)] + E, c_int),
+        "rt4_light_denoise_params_default": ([POINTER(LightDenoiseParams)], None),
+        "rt4_light_denoise_device": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_float, POINTER(LightDenoiseParams),
+                                      c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p] + E, c_int),
+        "rt4_light_denoise_host": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_float, POINTER(LightDenoiseParams),
+                                    c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int32, c_int32] + E, c_int),
+        "rt4_context_light_denoise_bytes": ([c_void_p], c_uint64),
     }
     tolerant = os.environ.get("RT4_AB_TOLERANT") == "1"  # tools/abtest.sh: older builds lack newer exports
     for name, (argtypes, restype) in sig.items():
@@ -367,7 +381,8 @@ EXPORTED = (
     "rt4_window_destroy rt4_window_reset rt4_window_present_device rt4_window_image rt4_window_gbuffer "
     "rt4_window_read_host rt4_window_bytes "
     "rt4_render_light_device rt4_render_light_host rt4_light_resolve_device rt4_light_resolve_host "
-    "rt4_light_noise_device rt4_light_noise_host"
+    "rt4_light_noise_device rt4_light_noise_host "
+    "rt4_light_denoise_params_default rt4_light_denoise_device rt4_light_denoise_host rt4_context_light_denoise_bytes"
 ).split()
 
 if ctypes.sizeof(SceneDesc) != lib.rt4_scene_desc_size() or ctypes.sizeof(Uniforms) != lib.rt4_uniforms_size():
@@ -559,6 +574,19 @@ def denoise_params(levels: int | None = None, cos_min: float | None = None, dept
     p = DenoiseParams()
     lib.rt4_denoise_params_default(byref(p))
     for name, v in (("levels", levels), ("cos_min", cos_min), ("depth_tol", depth_tol), ("max_refl_prob", max_refl_prob)):
+        if v is not None:
+            setattr(p, name, v)
+    return p
+
+
+def light_denoise_params(levels: int | None = None, cos_min: float | None = None, depth_tol: float | None = None,
+                         max_refl_prob: float | None = None, sigma: float | None = None,
+                         eps: float | None = None) -> LightDenoiseParams:
+    """rt4_light_denoise_params_default (5 levels, 0.9, 0.1, 0.5, sigma 4, eps 1e-6) with the given fields replaced."""
+    p = LightDenoiseParams()
+    lib.rt4_light_denoise_params_default(byref(p))
+    for name, v in (("levels", levels), ("cos_min", cos_min), ("depth_tol", depth_tol), ("max_refl_prob", max_refl_prob),
+                    ("sigma", sigma), ("eps", eps)):
         if v is not None:
             setattr(p, name, v)
     return p
@@ -1092,6 +1120,50 @@ class Tracer:
             len(err)), err)
         return se, q, tiles, {"pixels": st.pixels, "measured": st.measured, "above": st.above, "max_q": st.max_q,
                               "max_se": st.max_se}
+
+    def light_denoise_device(self, light_ptr: int, light_stride: int, gbuf_ptr: int, gbuf_stride: int, k: float,
+                             frame_ptr: int, fmt: int, frame_stride: int, w: int, h: int,
+                             params: LightDenoiseParams | None = None, filtered_ptr: int = 0, filtered_stride: int = 0,
+                             stream: int = 0) -> None:
+        """Asynchronous: the variance-guided a-trous filter of a device light accumulator, guided by the G-buffer of
+        the same view, tone-mapped with k into a frame of `fmt` (rt4_light_denoise_device). filtered_ptr: an optional
+        float4 image {L_r, L_g, L_b, V} (row stride in float4). For display: the accumulator is only read."""
+        p = params if params is not None else light_denoise_params()
+        err = _errbuf()
+        _check(self._lib.rt4_light_denoise_device(self._h, c_void_p(light_ptr or None), light_stride,
+                                                  c_void_p(gbuf_ptr or None), gbuf_stride, k, byref(p),
+                                                  c_void_p(frame_ptr or None), fmt, frame_stride,
+                                                  c_void_p(filtered_ptr or None), filtered_stride, w, h,
+                                                  c_void_p(stream or None), err, len(err)), err)
+
+    def light_denoise_host(self, light, gbuf, k: float, params: LightDenoiseParams | None = None, fmt: int = FRAME_RGBA32F,
+                           out=None, filtered=False, w: int | None = None):
+        """Synchronous: the filtered image of a host accumulator (h, stride) of LIGHT_DTYPE and a host G-buffer
+        (h, stride) of GBUFFER_DTYPE as (h, stride >= w, 4) of the format's dtype; w: the image width when rows are
+        padded. filtered: True for a new float32 (h, w, 4) array {L_r, L_g, L_b, V}, or an array (h, stride >= w, 4) to
+        write into. Returns `out` (a new array if None), or (out, filtered) when the filtered light was asked for."""
+        import numpy as np
+
+        assert light.dtype == LIGHT_DTYPE and light.flags["C_CONTIGUOUS"]
+        assert gbuf.dtype == GBUFFER_DTYPE and gbuf.flags["C_CONTIGUOUS"] and gbuf.shape[0] == light.shape[0]
+        h = light.shape[0]
+        w = light.shape[1] if w is None else w
+        if out is None:
+            out = np.zeros((h, w, 4), FRAME_NUMPY[fmt])
+        assert out.dtype == np.dtype(FRAME_NUMPY[fmt]) and out.flags["C_CONTIGUOUS"] and out.shape[0] == h
+        fl = np.zeros((h, w, 4), np.float32) if filtered is True else (filtered if filtered is not False else None)
+        assert fl is None or (fl.dtype == np.float32 and fl.flags["C_CONTIGUOUS"] and fl.shape[0] == h and fl.shape[2] == 4)
+        p = params if params is not None else light_denoise_params()
+        err = _errbuf()
+        _check(self._lib.rt4_light_denoise_host(
+            self._h, c_void_p(light.ctypes.data), light.shape[1], c_void_p(gbuf.ctypes.data), gbuf.shape[1], k, byref(p),
+            c_void_p(out.ctypes.data), fmt, out.shape[1], c_void_p(fl.ctypes.data) if fl is not None else None,
+            fl.shape[1] if fl is not None else 0, w, h, err, len(err)), err)
+        return out if fl is None else (out, fl)
+
+    def light_denoise_bytes(self) -> int:
+        """Bytes of the context's light-denoise scratch (rt4.h rt4_context_light_denoise_bytes)."""
+        return int(self._lib.rt4_context_light_denoise_bytes(self._h))
 
     @property
     def kernel_shape(self) -> int:

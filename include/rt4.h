@@ -801,6 +801,71 @@ int rt4_light_noise_host(rt4_context* ctx, const rt4_light_px* light, int64_t li
                          float threshold, float* se, float* q, int64_t map_stride, int32_t* tile_above,
                          rt4_noise_stats* stats, char* err, size_t errlen);
 
+/* ---- variance-guided a-trous filter of a light accumulator (no reference counterpart) ----
+ * The filter of rt4_denoise_device run on the light means instead of on tone-mapped colours, with a luminance
+ * edge-stop scaled by each pixel's own standard error, and tone-mapped once at the end (the SVGF scheme). Its support
+ * shrinks as the standard error does, so it neither inherits the tone-map bias of a colour average nor goes on
+ * blurring what varies inside one surface once the samples have resolved it. For display only: the accumulator is
+ * read, never written. A and G (the G-buffer of the same view) share the pixel indexing [0,w) x [0,h).
+ * Definition (fp32 round-to-nearest, no contraction, division and sqrt correctly rounded, fma explicit, dot the fma
+ * chain of DESIGN.md §3; comparisons with NaN are false and a NaN's payload is not defined; the kernels match it bit
+ * for bit):
+ *   Level 0. p is filterable iff G.surface >= 0 && G.refl_prob <= max_refl_prob && A.n >= 2. id(p) = the surface of a
+ *   filterable p, else -1. L_0 = A.mean, Y_0 = A.mean_y, V_0 = (A.m2 / (float)(n-1)) / (float)n (the radicand of se
+ *   in rt4_light_noise_device).
+ *   Level l = 0 .. levels-1, s = 2^l. A pixel that is not filterable keeps L, Y and V. For a filterable p:
+ *   1. The variance pre-filter at unit stride, G3 = {1/4, 1/2, 1/4}: dy = -1..1 (outer), dx = -1..1 (inner),
+ *      q = p + (dx, dy), g = G3[dy+1]*G3[dx+1]; a tap counts iff q == p, or q is inside the image and id(q) == id(p);
+ *      for a counted tap va = va + g*V_l(q) (a multiply, then an add) and vw = vw + g.
+ *      den = fma(sigma, sqrtf(va / vw), eps).
+ *   2. The 25 taps: order, q = p + s*(dx, dy), H and k = H[dy+2]*H[dx+2] as in rt4_denoise_device. The centre tap has
+ *      weight o = k. Any other tap passes the geometry test iff q is inside, id(q) == id(p), dot(n_p, n_q) >= cos_min
+ *      and fabsf(z_q - z_p) <= depth_tol * z_p; for such a tap t = fabsf(Y_l(q) - Y_l(p)) / den,
+ *      wl = 1.0f / fma(t, t, 1.0f), o = k * wl. A tap counts iff it is the centre, or it passes the geometry test and
+ *      o > 0. For a counted tap: aL_c = aL_c + o*L_l(q)_c; aY = aY + o*Y_l(q); aV = aV + (o*o)*V_l(q) (the square,
+ *      then the multiply, then the add); wsum = wsum + o.
+ *   3. L_{l+1} = aL / wsum, Y_{l+1} = aY / wsum, V_{l+1} = aV / (wsum*wsum).
+ *   The frame (any rt4_frame_format, alpha 1): a filterable pixel gets 1.0f - 1.0f / fma(k, L_levels_c, 1.0f) through
+ *   the format's store rule; every other pixel gets exactly what rt4_light_resolve_device writes. So levels = 0, or a
+ *   G-buffer of misses only, reproduces rt4_light_resolve_device byte for byte.
+ *   d_filtered (float4 per pixel, may be NULL): a filterable pixel gets {L_r, L_g, L_b, V} of the last level, any
+ *   other pixel {mean_r, mean_g, mean_b, n >= 2 ? V_0 : +inf}.
+ * Mirrors (refl_prob above max_refl_prob), the sky and pixels with fewer than two frames pass through unfiltered.
+ * With very few frames the variance estimate is poor (a pixel reads variance 0 until its first bright path arrives;
+ * the pre-filter borrows the neighbours'): the filter still beats no filter, but a geometry-only filter does better
+ * there. */
+#define RT4_LIGHT_DENOISE_MAX_LEVELS 6
+typedef struct rt4_light_denoise_params {
+  int32_t levels;      /* 0 .. RT4_LIGHT_DENOISE_MAX_LEVELS; 0 = no filtering (the plain resolve) */
+  float cos_min;       /* as rt4_denoise_params */
+  float depth_tol;     /* as rt4_denoise_params */
+  float max_refl_prob; /* as rt4_denoise_params */
+  float sigma;         /* luminance tolerance in standard errors */
+  float eps;           /* added to sigma * sd, in light units; >= 0 */
+} rt4_light_denoise_params;
+/* 5, 0.9f, 0.1f, 0.5f, 4.0f, 1e-6f: the values of the CPU prototype behind DESIGN.md §4.38's table (not tuned
+ * further; sigma = +inf makes the filter geometry-only wherever the variance is positive). */
+void rt4_light_denoise_params_default(rt4_light_denoise_params* p);
+/* Strides in elements of their image (d_filtered: in float4). RT4_ERR_ARG, nothing written, for a NULL required
+ * pointer, an unknown format, w or h outside [1, 65535], a stride below w, a misaligned pointer (accumulator, G-buffer
+ * and d_filtered 16 B, frame its pixel size), levels outside [0, RT4_LIGHT_DENOISE_MAX_LEVELS], sigma or eps negative
+ * or NaN, or an output that overlaps an input or the other output. Asynchronous on `stream`; ordered with the
+ * context's other launches. The levels and the repacked guide live in context-owned scratch of their own
+ * (rt4_context_light_denoise_bytes; rt4_context_denoise_bytes does not change): the first call that needs more waits
+ * for the stream and allocates; rt4_context_destroy frees it. */
+int rt4_light_denoise_device(rt4_context* ctx, const rt4_light_px* d_light, int64_t light_stride,
+                             const rt4_gbuffer_px* d_gbuf, int64_t gbuf_stride, float k,
+                             const rt4_light_denoise_params* params, void* d_frame, int32_t format, int64_t frame_stride,
+                             float* d_filtered, int64_t filtered_stride, int32_t w, int32_t h, void* stream, char* err,
+                             size_t errlen);
+/* The same on host buffers (synchronous; bytes outside [0,w) x [0,h) keep their values). */
+int rt4_light_denoise_host(rt4_context* ctx, const rt4_light_px* light, int64_t light_stride, const rt4_gbuffer_px* gbuf,
+                           int64_t gbuf_stride, float k, const rt4_light_denoise_params* params, void* frame,
+                           int32_t format, int64_t frame_stride, float* filtered, int64_t filtered_stride, int32_t w,
+                           int32_t h, char* err, size_t errlen);
+/* Bytes of the context's light-denoise scratch (0 before the first rt4_light_denoise_device call with levels > 0). */
+uint64_t rt4_context_light_denoise_bytes(const rt4_context* ctx);
+
 /* ---- diagnostics (used by the parity tests; not on the render path) ------------------------- */
 /* Bytes of the context's frame-colour scratch for pipelined frames (0 before any pipelined launch or
  * reservation; a scene that runs frame by frame never allocates it). */
