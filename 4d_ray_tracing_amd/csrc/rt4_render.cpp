@@ -45,6 +45,14 @@
 //                   accumulator through the variance-guided filter, rt4_render_gbuffer_device of the section's pose +
 //                   rt4_light_denoise_device, tone-mapped once at the end; with --window the filtered frame is the one
 //                   upscaled. Not with --denoise, which filters the resolved colours)
+//                   [--adaptive [--adaptive-warmup W] [--adaptive-pass F] [--adaptive-full-every M]
+//                    [--adaptive-min-above A] [--adaptive-dilate D]]  (needs --light: -n N becomes a budget of N
+//                   whole-frame equivalents, N x tiles tile-frames per section. W whole frames first, then passes of F
+//                   frames of the 8x8 tiles rt4_light_select_tiles_device picks for --noise-threshold (A hot pixels,
+//                   grown by D tiles), rendered by rt4_render_light_tiles_device; every M-th pass, and a pass with an
+//                   empty selection, is a whole-frame pass; the loop never stops early. One line per pass, the min /
+//                   median / max of n at the end, and <prefix>_<section>_n.<ext>: n over the largest n as grey.
+//                   Defaults 8, 4, 4, 4, 1: the values of the study in DESIGN.md §4.39)
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -330,6 +338,12 @@ int main(int argc, char** argv) {
   bool window_nearest = false;
   bool light = false, noise_map = false;  // --light, --noise-map
   float noise_threshold = 1.0f / 255.0f;  // --noise-threshold: one 8-bit step
+  // --adaptive (needs --light): the loop of DESIGN.md §4.39 in place of -n uniform frames; -n is then the budget in
+  // whole-frame equivalents. The defaults are the values of that section's study.
+  bool adaptive = false, ad_given = false;
+  int ad_warmup = 8, ad_pass = 4, ad_full_every = 4;  // --adaptive-warmup / --adaptive-pass / --adaptive-full-every
+  rt4_tile_select_params ad_select;                   // --adaptive-min-above / --adaptive-dilate; threshold: --noise-threshold
+  rt4_tile_select_params_default(&ad_select);
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -360,6 +374,12 @@ int main(int argc, char** argv) {
     else if (a == "--light") light = true;
     else if (a == "--noise-map") noise_map = true;
     else if (a == "--noise-threshold") noise_threshold = static_cast<float>(std::atof(next()));
+    else if (a == "--adaptive") adaptive = true;
+    else if (a == "--adaptive-warmup") ad_warmup = std::atoi(next()), ad_given = true;
+    else if (a == "--adaptive-pass") ad_pass = std::atoi(next()), ad_given = true;
+    else if (a == "--adaptive-full-every") ad_full_every = std::atoi(next()), ad_given = true;
+    else if (a == "--adaptive-min-above") ad_select.min_above = std::atoi(next()), ad_given = true;
+    else if (a == "--adaptive-dilate") ad_select.dilate = std::atoi(next()), ad_given = true;
     else if (a == "--window-nearest") {
       window_nearest = true;
       if (window_scale == 0) window_scale = -1;
@@ -399,6 +419,11 @@ int main(int argc, char** argv) {
   if (light && frame_by_frame) die("--light", "not with --frame-by-frame: the frames go through rt4_render_light_device");
   if (light && keys && move_seconds > 0.0f) die("--light", "needs a resting camera: the accumulator averages one view");
   if ((noise_map || noise_threshold != 1.0f / 255.0f) && !light) die("--noise-map / --noise-threshold", "need --light");
+  if ((adaptive || ad_given) && !light) die("--adaptive", "needs --light: it samples by the light accumulator's standard error");
+  if (ad_given && !adaptive) die("--adaptive-*", "need --adaptive");
+  if (adaptive && (ad_warmup < 0 || ad_pass < 1 || ad_full_every < 0 || ad_select.min_above < 1 || ad_select.min_above > 64 ||
+                   ad_select.dilate < 0 || ad_select.dilate > RT4_SELECT_MAX_DILATE || noise_threshold != noise_threshold))
+    die("--adaptive", "warmup >= 0, pass >= 1, full-every >= 0, min-above 1..64, dilate 0..2, a threshold that is a number");
   if (light_denoise_levels >= 0 && !light) die("--light-denoise", "needs --light: it filters the light accumulator");
   if (light_denoise_levels >= 0 && denoise_levels > 0)
     die("--light-denoise", "not with --denoise: one filtered frame per image");
@@ -551,6 +576,7 @@ int main(int argc, char** argv) {
   }
   rt4_uniforms last_u[3];  // the last frame's uniforms of every section: the camera pose the images show
   if (pipelined && !us.empty()) last_u[0] = us.back();
+  static const char* names[3] = {"yxz", "ywz", "yxw"};
   rt4_light_px* d_light[3] = {nullptr, nullptr, nullptr};  // --light: one accumulator per section
   for (int q = 0; q < n_img && light; q++) {
     HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_light[q]), static_cast<size_t>(cw[q]) * ch[q] * sizeof(rt4_light_px)));
@@ -570,7 +596,64 @@ int main(int argc, char** argv) {
                                             &lus[static_cast<size_t>(n - 1)]));
       last_u[q] = lus.back();
       const rt4_region reg{0, 0, cw[q], ch[q], 0, 0};
-      RT4_CHECK(rt4_render_light_device(ctx, lus.data(), frames, &reg, d_light[q], cw[q], d_count, nullptr, err, sizeof err));
+      if (adaptive) {
+        // The loop of DESIGN.md §4.39 (Tracer.render_light_adaptive is the same loop): warm-up whole frames, then passes
+        // of the selected tiles, every ad_full_every-th pass and a pass with an empty selection a whole frame; frame g is
+        // rt4_progressive_uniforms(the section's uniforms with --seed, g), g running on across the passes.
+        rt4_uniforms ub;
+        cam.frame_number = frame_number;
+        RT4_CHECK(rt4_camera_frame_uniforms(&cam, &base[q], sections[q], static_cast<int32_t>(seed), &ub));
+        cam.frame_number = frame_number + static_cast<uint32_t>(frames);  // as the uniform frames above left it
+        const long long tiles = static_cast<long long>((cw[q] + 7) / 8) * ((ch[q] + 7) / 8);
+        const long long budget = static_cast<long long>(frames) * tiles;
+        uint32_t *d_tiles = nullptr, *d_n = nullptr;
+        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_tiles), static_cast<size_t>(tiles) * sizeof(uint32_t)));
+        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_n), sizeof(uint32_t)));
+        rt4_tile_select_params sel = ad_select;
+        sel.threshold = noise_threshold;
+        long long spent = 0;
+        uint32_t g = 0;
+        std::vector<rt4_uniforms> pus;
+        auto pass_uniforms = [&](int n) {
+          pus.resize(static_cast<size_t>(n));
+          for (int f = 0; f < n; f++) rt4_progressive_uniforms(&ub, ++g, &pus[static_cast<size_t>(f)]);
+        };
+        const int warm = std::min(ad_warmup, frames);
+        sel.min_frames = warm;
+        if (warm > 0) {
+          pass_uniforms(warm);
+          RT4_CHECK(rt4_render_light_device(ctx, pus.data(), warm, &reg, d_light[q], cw[q], d_count, nullptr, err, sizeof err));
+          spent += warm * tiles;
+          std::printf("adaptive %s: warmup tiles %lld frames %d\n", names[q], tiles, warm);
+        }
+        for (int n_pass = 1;; n_pass++) {
+          const char* kind = "full";
+          long long listed = tiles;
+          if (!(ad_full_every > 0 && n_pass % ad_full_every == 0)) {
+            RT4_CHECK(rt4_light_select_tiles_device(ctx, d_light[q], cw[q], cw[q], ch[q], ub.light_to_color_conversion_coefficient,
+                                                    &sel, d_tiles, d_n, nullptr, nullptr, err, sizeof err));
+            uint32_t n_sel = 0;  // the one 4-byte read of the pass (synchronises)
+            HIP_CHECK(hipMemcpy(&n_sel, d_n, sizeof n_sel, hipMemcpyDeviceToHost));
+            kind = n_sel == 0 ? "empty" : "tiles";
+            if (n_sel != 0) listed = n_sel;
+          }
+          const int n = static_cast<int>(std::min<long long>(ad_pass, (budget - spent) / listed));
+          if (n <= 0) break;
+          pass_uniforms(n);
+          if (listed == tiles && kind[0] != 't')
+            RT4_CHECK(rt4_render_light_device(ctx, pus.data(), n, &reg, d_light[q], cw[q], d_count, nullptr, err, sizeof err));
+          else
+            RT4_CHECK(rt4_render_light_tiles_device(ctx, pus.data(), n, &reg, d_tiles, static_cast<int32_t>(listed), d_light[q],
+                                                    cw[q], d_count, nullptr, err, sizeof err));
+          spent += n * listed;
+          std::printf("adaptive %s: %s tiles %lld frames %d\n", names[q], kind, listed, n);
+        }
+        HIP_CHECK(hipDeviceSynchronize());
+        (void)hipFree(d_tiles);
+        (void)hipFree(d_n);
+      } else {
+        RT4_CHECK(rt4_render_light_device(ctx, lus.data(), frames, &reg, d_light[q], cw[q], d_count, nullptr, err, sizeof err));
+      }
       RT4_CHECK(rt4_light_resolve_device(ctx, d_light[q], cw[q], base[q].light_to_color_conversion_coefficient, d_frame[q],
                                          format, cw[q], cw[q], ch[q], nullptr, err, sizeof err));
     }
@@ -606,7 +689,6 @@ int main(int argc, char** argv) {
   unsigned long long count = 0;
   HIP_CHECK(hipMemcpy(&count, d_count, sizeof count, hipMemcpyDeviceToHost));
 
-  static const char* names[3] = {"yxz", "ywz", "yxw"};
   for (int q = 0; q < n_img; q++) {
     std::vector<unsigned char> host(static_cast<size_t>(cw[q]) * ch[q] * px);
     HIP_CHECK(hipMemcpy(host.data(), d_frame[q], host.size(), hipMemcpyDeviceToHost));
@@ -713,6 +795,26 @@ int main(int argc, char** argv) {
                   static_cast<unsigned long long>(ns.pixels), static_cast<unsigned long long>(ns.measured),
                   static_cast<unsigned long long>(ns.above), static_cast<double>(noise_threshold),
                   static_cast<double>(ns.max_q), static_cast<double>(ns.max_se));
+      if (adaptive) {
+        // where the frames went: min / median / max of n, and n over the largest n as grey
+        std::vector<rt4_light_px> acc(npx);
+        HIP_CHECK(hipMemcpy(acc.data(), d_light[q], npx * sizeof(rt4_light_px), hipMemcpyDeviceToHost));
+        std::vector<int32_t> nv(npx);
+        for (size_t p = 0; p < npx; p++) nv[p] = acc[p].n;
+        std::vector<int32_t> sorted = nv;
+        std::sort(sorted.begin(), sorted.end());
+        const int32_t n_max = sorted.back();
+        std::vector<float> grey(npx * 4);
+        for (size_t p = 0; p < npx; p++) {
+          grey[4 * p] = grey[4 * p + 1] = grey[4 * p + 2] = n_max > 0 ? static_cast<float>(nv[p]) / static_cast<float>(n_max) : 0.0f;
+          grey[4 * p + 3] = 1.0f;
+        }
+        const std::string n_path = out + "_" + names[q] + "_n" + (png ? ".png" : ".ppm");
+        RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(n_path.c_str(), grey.data(), RT4_FRAME_RGBA32F, cw[q], ch[q], cw[q], err,
+                                                        sizeof err));
+        std::printf("wrote %s (%d x %d, frames per pixel)\n", n_path.c_str(), cw[q], ch[q]);
+        std::printf("adaptive %s: n min %d, median %d, max %d\n", names[q], sorted.front(), sorted[npx / 2], n_max);
+      }
     }
     if (q == 0 && !checkpoint_path.empty()) {
       // frames_done counts camera-resting frames only: a moving camera restarts the blend (frame_number 1)

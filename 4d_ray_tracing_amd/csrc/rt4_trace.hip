@@ -1734,6 +1734,13 @@ struct rt4_context {
   // ({L, Y} 16 B, V 4 B) and the repacked guide (24 B), 64 B per pixel of the largest image filtered, in one allocation.
   void* d_light_denoise = nullptr;
   size_t light_denoise_px = 0;  // pixels it holds
+  // Scratch of adaptive light sampling (rt4_light_tiles.h): the per-tile flags of rt4_light_select_tiles_device, and the
+  // clamped copy of a tile list that rt4_render_light_tiles_device hands the trace kernel (followed by the two words
+  // {0, 1} it reads as KernelArgs::order_ends). Apart from d_order: the pre-pass order stays valid across tile launches.
+  uint32_t* d_select = nullptr;
+  size_t select_cap = 0;  // tiles it holds
+  uint32_t* d_tile_list = nullptr;
+  size_t tile_list_cap = 0;  // tiles it holds (+ 2 words)
 };
 
 #define HIP_TRY(expr)                                                                            \
@@ -2199,6 +2206,8 @@ void rt4_context_destroy(rt4_context* ctx) {
   if (ctx->d_eval) (void)hipFree(ctx->d_eval);
   if (ctx->d_denoise) (void)hipFree(ctx->d_denoise);
   if (ctx->d_light_denoise) (void)hipFree(ctx->d_light_denoise);
+  if (ctx->d_select) (void)hipFree(ctx->d_select);
+  if (ctx->d_tile_list) (void)hipFree(ctx->d_tile_list);
   delete ctx;
 }
 
@@ -2261,6 +2270,15 @@ struct LightTarget {
 };
 __global__ __launch_bounds__(256) void rt4_fold_light_kernel(const KernelArgs a, rt4_light_px* light, int64_t light_stride,
                                       unsigned long long* count_src, unsigned long long* count_dst);
+// A light launch of listed tiles only (rt4_render_light_tiles_device, rt4_light_tiles.h): n tile numbers of job 0 on the
+// device. The trace kernel gets a clamped copy as its order (stage_tile_list) and the fold runs over the listed tiles.
+struct TileList {
+  const uint32_t* d_tiles;
+  int32_t n;
+};
+int stage_tile_list(rt4_context* ctx, const TileList& tl, unsigned tiles, KernelArgs& a, hipStream_t s, char* err,
+                    size_t errlen);
+void launch_fold_light_tiles(const KernelArgs& a, const LightTarget& lt, hipStream_t s);
 
 // The trace kernel a launch of the context runs: its scene's shape, the sampler table, primary reuse.
 TraceFn trace_fn_of(const rt4_context* ctx) {
@@ -2309,7 +2327,7 @@ int ensure_overlap_buffer(rt4_context* ctx, unsigned k, size_t need, char* err, 
 
 int launch_jobs(rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, int32_t format,
                 unsigned long long* d_counter, void* stream, char* err, size_t errlen, const FramePlan* fp = nullptr,
-                const LightTarget* lt = nullptr) {
+                const LightTarget* lt = nullptr, const TileList* tl = nullptr) {
   if (!ctx || !jobs) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
   if (!ctx->has_scene) return rt4_set_err(err, errlen, "context has no scene (rt4_context_set_scene)"), RT4_ERR_ARG;
   if (n_jobs < 1 || n_jobs > RT4_MAX_SECTIONS)
@@ -2363,6 +2381,12 @@ int launch_jobs(rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, i
     a.n_frames = fp->n;
     a.frame_tiles = tiles;
     a.total = tiles * 64u * static_cast<unsigned>(fp->n);
+    if (tl) {  // the queue hands out the listed tiles only; `tiles` still sizes the checks above and the scratch
+      if (!lt || tl->n < 1 || static_cast<unsigned>(tl->n) > tiles)
+        return rt4_set_err(err, errlen, "tile list: bad length"), RT4_ERR_ARG;
+      a.frame_tiles = static_cast<unsigned>(tl->n);
+      a.total = a.frame_tiles * 64u * static_cast<unsigned>(fp->n);
+    }
     for (int f = 0; f < fp->n; f++) {
       a.frame_seed[f] = fp->seeds[f];
       a.frame_part[f] = fp->parts[f];
@@ -2488,6 +2512,10 @@ int launch_jobs(rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, i
   a.order_ends = ends;
   }
 #endif
+  if (tl && frames) {  // behind the waits above: the context's copy of the list is one per context, like d_order
+    const int st = stage_tile_list(ctx, *tl, tiles, a, ts, err, errlen);
+    if (st != RT4_OK) return st;
+  }
   // Queue words rotate; launch s zeroes launch s + S's word (launches up to s + S - 1 may already be running,
   // s + S starts only after s is complete): no memset between frames.
   unsigned* q = ctx->d_queue + (ctx->launch_seq % QUEUE_SLOTS);
@@ -2514,7 +2542,9 @@ int launch_jobs(rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, i
   if (le == hipSuccess && (frames || overlap)) {
     long long npx = 0;  // the largest image's pixels (blockIdx.y: the section)
     for (int q = 0; q < n_jobs; q++) npx = std::max(npx, static_cast<long long>(a.jobs[q].reg.w) * a.jobs[q].reg.h);
-    if (lt) {  // the light accumulator's fold in place of the colour fold (rt4_light.h)
+    if (lt && tl) {  // the fold of the listed tiles (rt4_light_tiles.h)
+      launch_fold_light_tiles(a, *lt, s);
+    } else if (lt) {  // the light accumulator's fold in place of the colour fold (rt4_light.h)
       hipLaunchKernelGGL(rt4_fold_light_kernel, dim3(static_cast<unsigned>((npx + 255) / 256)), dim3(256), 0, s, a, lt->light,
                          lt->row_stride_px, overlap ? count : nullptr, overlap ? d_counter : nullptr);
     } else {
@@ -3020,3 +3050,4 @@ int rt4_render_gbuffer_host(rt4_context* ctx, const rt4_uniforms* u, const rt4_r
 #include "rt4_upscale.h"
 #include "rt4_light.h"
 #include "rt4_light_denoise.h"
+#include "rt4_light_tiles.h"

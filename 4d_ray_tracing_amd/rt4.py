@@ -184,6 +184,13 @@ class LightDenoiseParams(Structure):  # rt4.h rt4_light_denoise_params
 LIGHT_DENOISE_MAX_LEVELS = 6
 
 
+class TileSelectParams(Structure):  # rt4.h rt4_tile_select_params
+    _fields_ = [("threshold", c_float), ("min_above", c_int32), ("min_frames", c_int32), ("dilate", c_int32)]
+
+
+SELECT_MAX_DILATE = 2  # rt4.h RT4_SELECT_MAX_DILATE
+
+
 def _gbuffer_dtype():
     import numpy as np
 
@@ -341,6 +348,16 @@ def _load(path=None):
         "rt4_light_denoise_host": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_float, POINTER(LightDenoiseParams),
                                     c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int32, c_int32] + E, c_int),
         "rt4_context_light_denoise_bytes": ([c_void_p], c_uint64),
+        "rt4_tile_select_params_default": ([POINTER(TileSelectParams)], None),
+        "rt4_light_select_tiles_device": ([c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float, POINTER(TileSelectParams),
+                                           c_void_p, c_void_p, c_void_p, c_void_p] + E, c_int),
+        "rt4_light_select_tiles_host": ([c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float, POINTER(TileSelectParams),
+                                         c_void_p, POINTER(c_uint32), c_void_p] + E, c_int),
+        "rt4_render_light_tiles_device": ([c_void_p, POINTER(Uniforms), c_int32, POINTER(Region), c_void_p, c_int32, c_void_p,
+                                           c_int64, c_void_p, c_void_p] + E, c_int),
+        "rt4_render_light_tiles_host": ([c_void_p, POINTER(Uniforms), c_int32, POINTER(Region), c_void_p, c_int32, c_void_p,
+                                         c_int64, POINTER(c_uint64)] + E, c_int),
+        "rt4_context_select_bytes": ([c_void_p], c_uint64),
     }
     tolerant = os.environ.get("RT4_AB_TOLERANT") == "1"  # tools/abtest.sh: older builds lack newer exports
     for name, (argtypes, restype) in sig.items():
@@ -382,7 +399,9 @@ EXPORTED = (
     "rt4_window_read_host rt4_window_bytes "
     "rt4_render_light_device rt4_render_light_host rt4_light_resolve_device rt4_light_resolve_host "
     "rt4_light_noise_device rt4_light_noise_host "
-    "rt4_light_denoise_params_default rt4_light_denoise_device rt4_light_denoise_host rt4_context_light_denoise_bytes"
+    "rt4_light_denoise_params_default rt4_light_denoise_device rt4_light_denoise_host rt4_context_light_denoise_bytes "
+    "rt4_tile_select_params_default rt4_light_select_tiles_device rt4_light_select_tiles_host "
+    "rt4_render_light_tiles_device rt4_render_light_tiles_host rt4_context_select_bytes"
 ).split()
 
 if ctypes.sizeof(SceneDesc) != lib.rt4_scene_desc_size() or ctypes.sizeof(Uniforms) != lib.rt4_uniforms_size():
@@ -590,6 +609,25 @@ def light_denoise_params(levels: int | None = None, cos_min: float | None = None
         if v is not None:
             setattr(p, name, v)
     return p
+
+
+def tile_select_params(threshold: float | None = None, min_above: int | None = None, min_frames: int | None = None,
+                       dilate: int | None = None) -> TileSelectParams:
+    """rt4_tile_select_params_default (threshold 1/255, min_above 4, min_frames 8, dilate 1: the values of the study in
+    DESIGN.md §4.39) with the given fields replaced."""
+    p = TileSelectParams()
+    lib.rt4_tile_select_params_default(byref(p))
+    for name, v in (("threshold", threshold), ("min_above", min_above), ("min_frames", min_frames), ("dilate", dilate)):
+        if v is not None:
+            setattr(p, name, v)
+    return p
+
+
+# The adaptive loop's defaults (Tracer.render_light_adaptive, rt4_render --light --adaptive): the values of the study in
+# DESIGN.md §4.39: whole frames first, frames per pass, every how many passes a whole-frame pass.
+ADAPTIVE_WARMUP = 8
+ADAPTIVE_PASS_FRAMES = 4
+ADAPTIVE_FULL_EVERY = 4
 
 
 def reproject_params(cos_min: float | None = None, plane_tol: float | None = None, slice_tol: float | None = None,
@@ -1164,6 +1202,127 @@ class Tracer:
     def light_denoise_bytes(self) -> int:
         """Bytes of the context's light-denoise scratch (rt4.h rt4_context_light_denoise_bytes)."""
         return int(self._lib.rt4_context_light_denoise_bytes(self._h))
+
+    def light_select_tiles_device(self, light_ptr: int, light_stride: int, w: int, h: int, k: float,
+                                  params: TileSelectParams | None, tiles_ptr: int, count_ptr: int, state_ptr: int = 0,
+                                  stream: int = 0) -> None:
+        """Asynchronous: the 8x8 tiles of a device accumulator worth more frames, ascending, into tiles_ptr (uint32,
+        ceil(w/8) * ceil(h/8) entries), their number into count_ptr (uint32) and, if state_ptr is not 0, 2 / 1 / 0 per
+        tile (int32: qualifies / selected by dilation / not selected). rt4_light_select_tiles_device."""
+        p = params if params is not None else tile_select_params()
+        err = _errbuf()
+        _check(self._lib.rt4_light_select_tiles_device(self._h, c_void_p(light_ptr or None), light_stride, w, h, k, byref(p),
+                                                       c_void_p(tiles_ptr or None), c_void_p(count_ptr or None),
+                                                       c_void_p(state_ptr or None), c_void_p(stream or None), err,
+                                                       len(err)), err)
+
+    def light_select_tiles_host(self, light, k: float, params: TileSelectParams | None = None, w: int | None = None,
+                                state=True):
+        """Synchronous: (tiles, state) of a host accumulator (h, stride) of LIGHT_DTYPE: the selected tiles as a uint32
+        array of the selected count, ascending, and the int32 (ceil(h/8), ceil(w/8)) state image (None with
+        state=False)."""
+        import numpy as np
+
+        assert light.dtype == LIGHT_DTYPE and light.flags["C_CONTIGUOUS"]
+        h = light.shape[0]
+        w = light.shape[1] if w is None else w
+        ty, tx = (h + 7) // 8, (w + 7) // 8
+        tiles = np.zeros(ty * tx, np.uint32)
+        st = np.zeros((ty, tx), np.int32) if state else None
+        n = c_uint32()
+        p = params if params is not None else tile_select_params()
+        err = _errbuf()
+        _check(self._lib.rt4_light_select_tiles_host(self._h, c_void_p(light.ctypes.data), light.shape[1], w, h, k, byref(p),
+                                                     c_void_p(tiles.ctypes.data), byref(n),
+                                                     c_void_p(st.ctypes.data) if st is not None else None, err, len(err)), err)
+        return tiles[:n.value].copy(), st
+
+    def render_light_tiles_device(self, us, reg: Region, tiles_ptr: int, n_tiles: int, light_ptr: int, row_stride_px: int,
+                                  counter_ptr: int = 0, stream: int = 0) -> None:
+        """Asynchronous: render_light_device for the n_tiles region-local tile numbers (uint32) at tiles_ptr only; every
+        other byte of the accumulator keeps its value (rt4_render_light_tiles_device). n_tiles is a host value."""
+        arr = (Uniforms * len(us))(*us)
+        err = _errbuf()
+        _check(self._lib.rt4_render_light_tiles_device(self._h, arr, len(us), byref(reg), c_void_p(tiles_ptr or None), n_tiles,
+                                                       c_void_p(light_ptr or None), row_stride_px,
+                                                       c_void_p(counter_ptr or None), c_void_p(stream or None), err,
+                                                       len(err)), err)
+
+    def render_light_tiles_host(self, us, reg: Region, tiles, light=None, row_stride_px: int | None = None):
+        """Synchronous: len(us) frames of the listed tiles folded onto a host accumulator (a new, empty one if None).
+        Returns (light, intersection count)."""
+        import numpy as np
+
+        if light is None:
+            light = np.zeros((reg.h, row_stride_px or reg.w), LIGHT_DTYPE)
+        assert light.dtype == LIGHT_DTYPE and light.flags["C_CONTIGUOUS"]
+        stride = row_stride_px if row_stride_px is not None else light.shape[1]
+        tiles = np.ascontiguousarray(tiles, np.uint32)
+        arr = (Uniforms * len(us))(*us)
+        n = c_uint64()
+        err = _errbuf()
+        _check(self._lib.rt4_render_light_tiles_host(self._h, arr, len(us), byref(reg),
+                                                     c_void_p(tiles.ctypes.data) if tiles.size else None, int(tiles.size),
+                                                     c_void_p(light.ctypes.data), stride, byref(n), err, len(err)), err)
+        return light, n.value
+
+    def select_bytes(self) -> int:
+        """Bytes of the context's tile scratch (rt4.h rt4_context_select_bytes)."""
+        return int(self._lib.rt4_context_select_bytes(self._h))
+
+    def render_light_adaptive(self, base: Uniforms, w: int, h: int, budget_frames: int, select: TileSelectParams | None = None,
+                              warmup: int = ADAPTIVE_WARMUP, pass_frames: int = ADAPTIVE_PASS_FRAMES,
+                              full_every: int = ADAPTIVE_FULL_EVERY, light=None):
+        """The adaptive loop of DESIGN.md §4.39 on a host accumulator (h, w) of LIGHT_DTYPE (a new, empty one if None),
+        the loop rt4_render --light --adaptive runs. The budget is budget_frames whole-frame equivalents:
+        budget_frames * tiles tile-frames. `warmup` whole frames first (select.min_frames is set to it), then passes of
+        pass_frames frames of the selected tiles; every full_every-th pass (0: never), and a pass whose selection is
+        empty, is a whole-frame pass. Frame g uses progressive_uniforms(base, g), g running on across passes. The last
+        pass is clipped to the frames the remaining budget pays for; the loop never stops early. Returns (light,
+        intersection count, log) with log a list of (kind, listed tiles, frames), kind one of "warmup", "full", "empty",
+        "tiles"."""
+        import numpy as np
+
+        if light is None:
+            light = np.zeros((h, w), LIGHT_DTYPE)
+        assert light.dtype == LIGHT_DTYPE and light.shape == (h, w) and light.flags["C_CONTIGUOUS"]
+        reg = region(w, h)
+        tiles = ((w + 7) // 8) * ((h + 7) // 8)
+        budget = budget_frames * tiles
+        sel = TileSelectParams.from_buffer_copy(bytes(select if select is not None else tile_select_params()))
+        k = base.light_to_color_conversion_coefficient
+        count, spent, g, log = 0, 0, 0, []
+
+        def frames(n):
+            nonlocal g
+            us = [progressive_uniforms(base, f) for f in range(g + 1, g + n + 1)]
+            g += n
+            return us
+
+        warm = min(warmup, budget_frames)
+        sel.min_frames = warm
+        if warm > 0:
+            count += self.render_light_host(frames(warm), reg, light)[1]
+            spent += warm * tiles
+            log.append(("warmup", tiles, warm))
+        n_pass = 0
+        while True:
+            n_pass += 1
+            kind, listed, lst = "full", tiles, None
+            if not (full_every > 0 and n_pass % full_every == 0):
+                lst, _ = self.light_select_tiles_host(light, k, sel, state=False)
+                if len(lst) == 0:
+                    kind, lst = "empty", None
+                else:
+                    kind, listed = "tiles", len(lst)
+            n = min(pass_frames, (budget - spent) // listed)
+            if n <= 0:
+                break
+            us = frames(n)
+            count += (self.render_light_host(us, reg, light) if lst is None else self.render_light_tiles_host(us, reg, lst, light))[1]
+            spent += n * listed
+            log.append((kind, listed, n))
+        return light, count, log
 
     @property
     def kernel_shape(self) -> int:

@@ -866,6 +866,65 @@ int rt4_light_denoise_host(rt4_context* ctx, const rt4_light_px* light, int64_t 
 /* Bytes of the context's light-denoise scratch (0 before the first rt4_light_denoise_device call with levels > 0). */
 uint64_t rt4_context_light_denoise_bytes(const rt4_context* ctx);
 
+/* ---- adaptive light sampling: select noisy tiles, render only those (no reference counterpart) ----
+ * The light accumulator keeps a frame count and a standard error per pixel; these two calls let a caller spend its
+ * frames where that error is large. The policy (how many whole frames first, how often a whole frame again, when to
+ * stop) stays with the caller: Tracer.render_light_adaptive (rt4.py) and rt4_render --light --adaptive run one.
+ * Choosing samples from a pixel's own earlier samples is optional stopping: it biases the mean (DESIGN.md §4.39 has
+ * the measured sizes). Dilation, the min_frames floor and periodic whole frames reduce the bias; none removes it.
+ * Selection. Tiles are 8x8, numbered ty * tiles_x + tx with tiles_x = ceil(w/8): the numbering of d_tile_above. Only
+ * pixels inside [0,w) x [0,h) count (never a padded row's padding).
+ *   A pixel is hot iff n >= 2 && q > threshold, q op for op as in rt4_light_noise_device (false for a NaN q).
+ *   A pixel is young iff n < min_frames.
+ *   A tile qualifies iff it holds a young pixel or at least min_above hot pixels.
+ *   A tile is selected iff some tile (tx+dx, ty+dy) inside the tile grid with |dx|, |dy| <= dilate qualifies (no
+ *   wrap-around from the end of one tile row to the start of the next).
+ * d_tiles[0 .. count) receives the selected tiles in ascending order (exact and deterministic); entries from count on
+ * keep their bytes; d_tiles must hold tiles_x * tiles_y entries. *d_count receives count. d_tile_state (may be NULL;
+ * tiles_x * tiles_y entries) receives 2 for a qualifying tile, 1 for a tile selected only by dilation, else 0. */
+#define RT4_SELECT_MAX_DILATE 2
+typedef struct rt4_tile_select_params {
+  float threshold;    /* q threshold in display units, as rt4_light_noise_device; NaN is RT4_ERR_ARG */
+  int32_t min_above;  /* 1..64: hot pixels a tile needs to qualify */
+  int32_t min_frames; /* >= 0: a tile holding a pixel with n < min_frames qualifies whatever its noise */
+  int32_t dilate;     /* 0..RT4_SELECT_MAX_DILATE: also take the tiles this close to a qualifying one */
+} rt4_tile_select_params;
+/* 1.0f / 255.0f (one 8-bit step), 4, 8, 1: the values of the CPU study behind DESIGN.md §4.39's table (not tuned further). */
+void rt4_tile_select_params_default(rt4_tile_select_params* p);
+/* RT4_ERR_ARG, nothing written, for a NULL pointer (d_tile_state excepted), w or h outside [1, 65535], a stride below w,
+ * a misaligned pointer (accumulator 16 B, the others 4 B), a parameter outside its range, or an output that overlaps
+ * the accumulator or another output. Asynchronous on `stream`; ordered with the context's other launches. The
+ * per-tile flags live in context-owned scratch (rt4_context_select_bytes): the first call with more tiles than any
+ * before waits for the stream and allocates; rt4_context_destroy frees it. */
+int rt4_light_select_tiles_device(rt4_context* ctx, const rt4_light_px* d_light, int64_t light_stride, int32_t w, int32_t h,
+                                  float k, const rt4_tile_select_params* params, uint32_t* d_tiles, uint32_t* d_count,
+                                  int32_t* d_tile_state, void* stream, char* err, size_t errlen);
+/* The same on host buffers (synchronous; tiles: tiles_x * tiles_y entries, those from *count on keep their bytes). */
+int rt4_light_select_tiles_host(rt4_context* ctx, const rt4_light_px* light, int64_t light_stride, int32_t w, int32_t h,
+                                float k, const rt4_tile_select_params* params, uint32_t* tiles, uint32_t* count,
+                                int32_t* tile_state, char* err, size_t errlen);
+/* rt4_render_light_device for the n_tiles listed tiles only. Tile numbers are region-local: ty * tiles_x + tx with
+ * tiles_x = ceil(region.w/8), so for a whole-image region the numbering of selection; a banded or offset region
+ * numbers its own rows. n_tiles is a host value (the caller reads *d_count back: one 4-byte read per pass). The
+ * pixels of the listed tiles hold exactly the bytes rt4_render_light_device with the same u, n_frames and region
+ * would have left in them; every other byte of d_light keeps its value; d_counter grows by the find_intersection calls
+ * of the listed tiles' pixels only. n_tiles == 0 is RT4_OK and launches nothing. With tiles = tiles_x * tiles_y:
+ * entries >= tiles are ignored; a tile listed twice leaves that tile's pixels unspecified (one or two applications of
+ * each frame), never anything out of bounds. RT4_ERR_ARG for n_tiles < 0 or > tiles, a NULL or misaligned (4 B) list
+ * with n_tiles > 0, and everything rt4_render_light_device refuses. The list is copied (clamped) into context-owned
+ * scratch first, counted in rt4_context_select_bytes and sized for the region: the first call for a region with more
+ * tiles than any before waits for the stream and allocates; after that the call neither synchronises nor allocates.
+ * Asynchronous; ordered with the context's other launches. */
+int rt4_render_light_tiles_device(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, const rt4_region* region,
+                                  const uint32_t* d_tiles, int32_t n_tiles, rt4_light_px* d_light, int64_t row_stride_px,
+                                  unsigned long long* d_counter, void* stream, char* err, size_t errlen);
+/* The same with a host list onto a host accumulator (synchronous). n_intersections (may be NULL) receives the count. */
+int rt4_render_light_tiles_host(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, const rt4_region* region,
+                                const uint32_t* tiles, int32_t n_tiles, rt4_light_px* light, int64_t row_stride_px,
+                                uint64_t* n_intersections, char* err, size_t errlen);
+/* Bytes of the context's tile scratch: the selection's flags and the render's list copy (0 before the first call). */
+uint64_t rt4_context_select_bytes(const rt4_context* ctx);
+
 /* ---- diagnostics (used by the parity tests; not on the render path) ------------------------- */
 /* Bytes of the context's frame-colour scratch for pipelined frames (0 before any pipelined launch or
  * reservation; a scene that runs frame by frame never allocates it). */
