@@ -1,6 +1,6 @@
 // rt4_denoise.h — the edge-stopping a-trous filter of rt4.h (rt4_denoise_device): kernels and
-// entry points. Part of rt4_trace.hip's translation unit (included at its end: the context, the blend_* store
-// helpers and the launch ordering live there); no trace kernel uses anything from here.
+// entry points. From rt4_post.h: the argument checks, the launch bracket, the pixel grid, px_decode, HostStage and
+// grow_scratch; from no other pass. No trace kernel uses anything from here.
 //
 // One call: a pack pass decodes the input frame to fp32 (level 0) and repacks the G-buffer into the guide
 // (normal 16 B; {id, depth} 8 B with id = the surface of a filterable pixel, else -1), then one pass per level
@@ -13,9 +13,8 @@
 
 namespace {
 
-constexpr int DN_BX = 32, DN_BY = 8;                    // pixels per workgroup (one lane each)
 constexpr int DN_MAX_TILED_STEP = 2;                    // strides staged in LDS
-constexpr int DN_TILE_MAX = (DN_BX + 4 * DN_MAX_TILED_STEP) * (DN_BY + 4 * DN_MAX_TILED_STEP);  // 40 x 16 pixels
+constexpr int DN_TILE_MAX = (PX_BX + 4 * DN_MAX_TILED_STEP) * (PX_BY + 4 * DN_MAX_TILED_STEP);  // 40 x 16 pixels
 
 struct DnArgs {
   int32_t w, h, step;
@@ -36,21 +35,10 @@ __global__ __launch_bounds__(256) void rt4_denoise_pack_kernel(const void* __res
                                                                int32_t w, int32_t h, float max_refl_prob,
                                                                float4* __restrict__ c0, float4* __restrict__ gn,
                                                                int2* __restrict__ gi) {
-  const int x = static_cast<int>(blockIdx.x) * DN_BX + static_cast<int>(threadIdx.x & 31u);
-  const int y = static_cast<int>(blockIdx.y) * DN_BY + static_cast<int>(threadIdx.x >> 5);
+  const int2 xy = px_xy();
+  const int x = xy.x, y = xy.y;
   if (x >= w || y >= h) return;
-  const int64_t at = static_cast<int64_t>(y) * in_stride + x;
-  float4 c;
-  if (format == RT4_FRAME_RGBA16F) {
-    const h4v v = reinterpret_cast<const h4v*>(in)[at];
-    c = make_float4(static_cast<float>(v[0]), static_cast<float>(v[1]), static_cast<float>(v[2]), static_cast<float>(v[3]));
-  } else if (format == RT4_FRAME_RGBA8) {
-    const uint32_t v = reinterpret_cast<const uint32_t*>(in)[at];
-    c = make_float4(static_cast<float>(v & 0xFFu) / 255.0f, static_cast<float>((v >> 8) & 0xFFu) / 255.0f,
-                    static_cast<float>((v >> 16) & 0xFFu) / 255.0f, static_cast<float>(v >> 24) / 255.0f);
-  } else {
-    c = reinterpret_cast<const float4*>(in)[at];
-  }
+  const float4 c = px_decode(in, format, static_cast<int64_t>(y) * in_stride + x);
   const float4* g = reinterpret_cast<const float4*>(gbuf + static_cast<int64_t>(y) * gbuf_stride + x);
   const float4 n = g[0], m = g[1];  // m: depth, surface, refl_prob, glow
   const int surface = __float_as_int(m.y);
@@ -70,12 +58,12 @@ __global__ __launch_bounds__(256) void rt4_denoise_level_kernel(const DnArgs a) 
       l_nw[TILED ? DN_TILE_MAX : 1], l_z[TILED ? DN_TILE_MAX : 1];
   __shared__ int l_id[TILED ? DN_TILE_MAX : 1];
   const int tx = static_cast<int>(threadIdx.x & 31u), ty = static_cast<int>(threadIdx.x >> 5);
-  const int ox = static_cast<int>(blockIdx.x) * DN_BX, oy = static_cast<int>(blockIdx.y) * DN_BY;
+  const int ox = static_cast<int>(blockIdx.x) * PX_BX, oy = static_cast<int>(blockIdx.y) * PX_BY;
   const int x = ox + tx, y = oy + ty;
   const int s = a.step, w = a.w, h = a.h;
-  const int R = 2 * s, T = DN_BX + 2 * R;  // halo, LDS row pitch (TILED)
+  const int R = 2 * s, T = PX_BX + 2 * R;  // halo, LDS row pitch (TILED)
   if (TILED) {
-    const int n = T * (DN_BY + 2 * R);  // <= DN_TILE_MAX: the host launches this instantiation for s <= 2 only
+    const int n = T * (PX_BY + 2 * R);  // <= DN_TILE_MAX: the host launches this instantiation for s <= 2 only
     for (int k = static_cast<int>(threadIdx.x); k < n; k += 256) {
       const int ly = k / T, lx = k - ly * T;
       const int gx = ox - R + lx, gy = oy - R + ly;
@@ -184,113 +172,86 @@ __global__ __launch_bounds__(256) void rt4_denoise_level_kernel(const DnArgs a) 
 
 extern "C" {
 
-uint64_t rt4_context_denoise_bytes(const rt4_context* ctx) { return ctx ? static_cast<uint64_t>(ctx->denoise_px) * 56u : 0u; }
+uint64_t rt4_context_denoise_bytes(const rt4_context* ctx) { return ctx ? static_cast<uint64_t>(ctx->denoise.cap) * 56u : 0u; }
 
 int rt4_denoise_device(rt4_context* ctx, const void* d_in, int64_t in_stride_px, void* d_out, int64_t out_stride_px,
                        int32_t format, int32_t w, int32_t h, const rt4_gbuffer_px* d_gbuf, int64_t gbuf_stride_px,
                        const rt4_denoise_params* params, void* stream, char* err, size_t errlen) {
   if (!ctx || !d_in || !d_out || !d_gbuf || !params) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
-  const int32_t px_bytes = rt4_frame_format_bytes(format);
+  const size_t px_bytes = static_cast<size_t>(rt4_frame_format_bytes(format));
   if (px_bytes == 0) return rt4_set_err(err, errlen, "unknown frame format %d", format), RT4_ERR_ARG;
   if (w <= 0 || h <= 0 || w > 65535 || h > 65535)
     return rt4_set_err(err, errlen, "frame size %d x %d not in [1, 65535]", w, h), RT4_ERR_ARG;
-  if (in_stride_px < w || out_stride_px < w || gbuf_stride_px < w)
-    return rt4_set_err(err, errlen, "row stride smaller than width"), RT4_ERR_ARG;
   if (params->levels < 1 || params->levels > RT4_DENOISE_MAX_LEVELS)
     return rt4_set_err(err, errlen, "levels %d not in [1, %d]", params->levels, RT4_DENOISE_MAX_LEVELS), RT4_ERR_ARG;
-  const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_in), out0 = reinterpret_cast<uintptr_t>(d_out);
-  const uintptr_t in1 = in0 + image_span(in_stride_px, w, h) * px_bytes, out1 = out0 + image_span(out_stride_px, w, h) * px_bytes;
-  if (in0 < out1 && out0 < in1) return rt4_set_err(err, errlen, "d_in and d_out overlap"), RT4_ERR_ARG;
-  if (in0 % px_bytes != 0 || out0 % px_bytes != 0 || reinterpret_cast<uintptr_t>(d_gbuf) % 16u != 0)
-    return rt4_set_err(err, errlen, "frame or G-buffer not aligned to its pixel size"), RT4_ERR_ARG;
+  // rt4.h promises the overlap check for d_in and d_out only: the G-buffer is checked for itself
+  const PostImage in = post_image(d_in, in_stride_px, w, h, px_bytes, "d_in");
+  const PostImage out = post_image(d_out, out_stride_px, w, h, px_bytes, "d_out");
+  int st = post_check_image(post_image(d_gbuf, gbuf_stride_px, w, h, sizeof(rt4_gbuffer_px), "G-buffer"), err, errlen);
+  if (st == RT4_OK) st = post_check_args(&out, 1, &in, 1, err, errlen);
+  if (st != RT4_OK) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const size_t npx = static_cast<size_t>(w) * static_cast<size_t>(h);
-  if (ctx->denoise_px < npx) {  // a larger frame than any before: wait for the launches in flight, grow once
-    HIP_TRY(hipStreamSynchronize(s));
-    if (ctx->launched) HIP_TRY(hipEventSynchronize(ctx->done));
-    if (ctx->d_denoise) (void)hipFree(ctx->d_denoise);
-    ctx->d_denoise = nullptr;
-    ctx->denoise_px = 0;
-    HIP_TRY(hipMalloc(&ctx->d_denoise, npx * 56u));
-    ctx->denoise_px = npx;
-  }
+  // a larger frame than any before grows the scratch once
+  st = grow_scratch(ctx, ctx->denoise, s, static_cast<size_t>(w) * static_cast<size_t>(h), 56u, err, errlen);
+  if (st != RT4_OK) return st;
   // the four arrays of the scratch, each for the context's largest frame (16-B aligned: multiples of 16 B)
-  char* base = static_cast<char*>(ctx->d_denoise);
-  float4* level[2] = {reinterpret_cast<float4*>(base), reinterpret_cast<float4*>(base + ctx->denoise_px * 16u)};
-  float4* gn = reinterpret_cast<float4*>(base + ctx->denoise_px * 32u);
-  int2* gi = reinterpret_cast<int2*>(base + ctx->denoise_px * 48u);
-  int rc = order_launch(ctx, s, err, errlen);
-  if (rc != RT4_OK) return rc;
-  const dim3 grid(static_cast<unsigned>((w + DN_BX - 1) / DN_BX), static_cast<unsigned>((h + DN_BY - 1) / DN_BY)), block(256);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(rt4_denoise_pack_kernel, grid, block, 0, s, d_in, in_stride_px, format, d_gbuf, gbuf_stride_px, w, h,
-                     params->max_refl_prob, level[0], gn, gi);
-  hipError_t le = hipGetLastError();
-  for (int32_t l = 0; l < params->levels && le == hipSuccess; l++) {
-    DnArgs a;
-    a.w = w;
-    a.h = h;
-    a.step = 1 << l;
-    a.cos_min = params->cos_min;
-    a.depth_tol = params->depth_tol;
-    a.src = level[l & 1];
-    a.gn = gn;
-    a.gi = gi;
-    a.dst = l + 1 < params->levels ? level[(l + 1) & 1] : nullptr;
-    a.in = d_in;
-    a.out = d_out;
-    a.in_stride = in_stride_px;
-    a.out_stride = out_stride_px;
-    a.format = format;
-    if (a.step <= DN_MAX_TILED_STEP) hipLaunchKernelGGL(rt4_denoise_level_kernel<true>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(rt4_denoise_level_kernel<false>, grid, block, 0, s, a);
-    le = hipGetLastError();
-  }
-  rc = done_launch(ctx, s, err, errlen);
-  if (le != hipSuccess) {
-    rt4_set_err(err, errlen, "denoise kernel launch failed: %s", hipGetErrorString(le));
-    return RT4_ERR_HIP;
-  }
-  return rc;
+  char* base = static_cast<char*>(ctx->denoise.d);
+  float4* level[2] = {reinterpret_cast<float4*>(base), reinterpret_cast<float4*>(base + ctx->denoise.cap * 16u)};
+  float4* gn = reinterpret_cast<float4*>(base + ctx->denoise.cap * 32u);
+  int2* gi = reinterpret_cast<int2*>(base + ctx->denoise.cap * 48u);
+  return post_launch(ctx, s, "denoise kernel", err, errlen, [&] {
+    const dim3 grid = px_grid(w, h), block(256);
+    hipLaunchKernelGGL(rt4_denoise_pack_kernel, grid, block, 0, s, d_in, in_stride_px, format, d_gbuf, gbuf_stride_px, w, h,
+                       params->max_refl_prob, level[0], gn, gi);
+    hipError_t le = hipGetLastError();
+    for (int32_t l = 0; l < params->levels && le == hipSuccess; l++) {
+      DnArgs a;
+      a.w = w;
+      a.h = h;
+      a.step = 1 << l;
+      a.cos_min = params->cos_min;
+      a.depth_tol = params->depth_tol;
+      a.src = level[l & 1];
+      a.gn = gn;
+      a.gi = gi;
+      a.dst = l + 1 < params->levels ? level[(l + 1) & 1] : nullptr;
+      a.in = d_in;
+      a.out = d_out;
+      a.in_stride = in_stride_px;
+      a.out_stride = out_stride_px;
+      a.format = format;
+      if (a.step <= DN_MAX_TILED_STEP) hipLaunchKernelGGL(rt4_denoise_level_kernel<true>, grid, block, 0, s, a);
+      else hipLaunchKernelGGL(rt4_denoise_level_kernel<false>, grid, block, 0, s, a);
+      le = hipGetLastError();
+    }
+    return le;
+  });
 }
 
 int rt4_denoise_host(rt4_context* ctx, const void* in, int64_t in_stride_px, void* out, int64_t out_stride_px,
                      int32_t format, int32_t w, int32_t h, const rt4_gbuffer_px* gbuf, int64_t gbuf_stride_px,
                      const rt4_denoise_params* params, char* err, size_t errlen) {
   if (!ctx || !in || !out || !gbuf || !params) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
-  const int32_t px_bytes = rt4_frame_format_bytes(format);
+  const size_t px_bytes = static_cast<size_t>(rt4_frame_format_bytes(format));
   if (px_bytes == 0) return rt4_set_err(err, errlen, "unknown frame format %d", format), RT4_ERR_ARG;
   if (w <= 0 || h <= 0 || in_stride_px < w || out_stride_px < w || gbuf_stride_px < w)
     return rt4_set_err(err, errlen, "bad frame size or row stride"), RT4_ERR_ARG;
-  const size_t in_bytes = image_span(in_stride_px, w, h) * px_bytes, out_bytes = image_span(out_stride_px, w, h) * px_bytes;
-  const size_t g_bytes = image_span(gbuf_stride_px, w, h) * sizeof(rt4_gbuffer_px);
-  const char *i0 = static_cast<const char*>(in), *o0 = static_cast<const char*>(out);
-  if (i0 < o0 + out_bytes && o0 < i0 + in_bytes) return rt4_set_err(err, errlen, "in and out overlap"), RT4_ERR_ARG;
+  const PostImage hi = post_image(in, in_stride_px, w, h, px_bytes, "in"), ho = post_image(out, out_stride_px, w, h, px_bytes, "out");
+  if (post_check_overlap(&ho, 1, &hi, 1, err, errlen) != RT4_OK) return RT4_ERR_ARG;  // the host images themselves
   HIP_TRY(hipSetDevice(ctx->device));
-  void *di = nullptr, *dout = nullptr, *dg = nullptr;
-  hipError_t e = hipMalloc(&di, in_bytes);
-  if (e == hipSuccess) e = hipMalloc(&dout, out_bytes);
-  if (e == hipSuccess) e = hipMalloc(&dg, g_bytes);
-  if (e == hipSuccess) e = hipMemcpy(di, in, in_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dout, out, out_bytes, hipMemcpyHostToDevice);  // the padding keeps its bytes
-  if (e == hipSuccess) e = hipMemcpy(dg, gbuf, g_bytes, hipMemcpyHostToDevice);
-  int st = RT4_OK;
+  HostStage di, dout, dg;
+  hipError_t e = di.up(in, post_bytes(hi));
+  if (e == hipSuccess) e = dout.up(out, post_bytes(ho));
+  if (e == hipSuccess) e = dg.up(gbuf, image_span(gbuf_stride_px, w, h) * sizeof(rt4_gbuffer_px));
   if (e == hipSuccess) {
-    st = rt4_denoise_device(ctx, di, in_stride_px, dout, out_stride_px, format, w, h, static_cast<const rt4_gbuffer_px*>(dg),
-                            gbuf_stride_px, params, nullptr, err, errlen);
-    if (st == RT4_OK) {
-      e = hipDeviceSynchronize();
-      if (e == hipSuccess) e = hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost);
-    }
+    const int st = rt4_denoise_device(ctx, di.d, in_stride_px, dout.d, out_stride_px, format, w, h, dg.as<const rt4_gbuffer_px>(),
+                                      gbuf_stride_px, params, nullptr, err, errlen);
+    if (st != RT4_OK) return st;
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = dout.down(out);
   }
-  if (di) (void)hipFree(di);
-  if (dout) (void)hipFree(dout);
-  if (dg) (void)hipFree(dg);
-  if (st == RT4_OK && e != hipSuccess) {
-    rt4_set_err(err, errlen, "denoise_host failed: %s", hipGetErrorString(e));
-    st = RT4_ERR_HIP;
-  }
-  return st;
+  if (e != hipSuccess) return rt4_set_err(err, errlen, "denoise_host failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
+  return RT4_OK;
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // rt4_light.h — light-domain accumulation of rt4.h (rt4_render_light_device, rt4_light_resolve_device,
-// rt4_light_noise_device): kernels and entry points. Part of rt4_trace.hip's translation unit (included
-// at its end, after rt4_upscale.h: the context, KernelArgs, launch_jobs, the blend_* store helpers, the launch ordering
-// and rp_span / rp_overlap live there); no trace kernel uses anything from here.
+// rt4_light_noise_device): kernels and entry points. From rt4_post.h: the argument checks, the launch
+// bracket, the pixel grid, px_store_opaque and HostStage; from no other pass (KernelArgs, launch_jobs and TileList are
+// rt4_trace.hip's). rt4_light_denoise.h and rt4_light_tiles.h take light_tone, light_apply, LIGHT_LOAD_BATCH and
+// render_light / render_light_staged from here. No trace kernel uses anything from here.
 //
 // The trace kernels already hand every frame's raw light sum to the frame-colour scratch (KernelArgs::fcolor); the
 // colour accumulators tone-map it in rt4_fold_frames_kernel. The light accumulator is a second fold over the same
@@ -68,8 +69,6 @@ __global__ __launch_bounds__(256) void rt4_fold_light_kernel(const KernelArgs a,
   st[1] = make_float4(m2, __int_as_float(n), 0.0f, 0.0f);
 }
 
-constexpr int LT_BX = 32, LT_BY = 8;  // resolve: pixels per workgroup (one lane each)
-
 // rt4.h: the tone curve of tone_map on a mean (the same ops).
 __device__ __forceinline__ float light_tone(float k, float v) { return 1.0f - 1.0f / sfma_(k, v, 1.0f); }
 
@@ -77,24 +76,14 @@ __device__ __forceinline__ float light_tone(float k, float v) { return 1.0f - 1.
 __global__ __launch_bounds__(256) void rt4_light_resolve_kernel(const rt4_light_px* __restrict__ light, int64_t light_stride,
                                                                 float k, void* __restrict__ frame, int32_t format,
                                                                 int64_t frame_stride, int32_t w, int32_t h) {
-  const int x = static_cast<int>(blockIdx.x) * LT_BX + static_cast<int>(threadIdx.x & 31u);
-  const int y = static_cast<int>(blockIdx.y) * LT_BY + static_cast<int>(threadIdx.x >> 5);
+  const int2 xy = px_xy();
+  const int x = xy.x, y = xy.y;
   if (x >= w || y >= h) return;
   const float4* st = reinterpret_cast<const float4*>(light + static_cast<int64_t>(y) * light_stride + x);
   const float4 m = st[0];
   const int32_t n = __float_as_int(st[1].y);
-  // blend_*(c, 1, 0) is the store rule of the format (rt4_temporal.h does the same)
   const V3 c = n == 0 ? V3{0.0f, 0.0f, 0.0f} : V3{light_tone(k, m.x), light_tone(k, m.y), light_tone(k, m.z)};
-  const int64_t at = static_cast<int64_t>(y) * frame_stride + x;
-  if (format == RT4_FRAME_RGBA16F) {
-    h4v zero;
-    zero[0] = zero[1] = zero[2] = zero[3] = static_cast<_Float16>(0.0f);
-    reinterpret_cast<h4v*>(frame)[at] = blend_f16(c, 1.0f, zero);
-  } else if (format == RT4_FRAME_RGBA8) {
-    reinterpret_cast<uint32_t*>(frame)[at] = blend_u8(c, 1.0f, 0u);
-  } else {
-    reinterpret_cast<float4*>(frame)[at] = blend_f32(c, 1.0f, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-  }
+  px_store_opaque(frame, format, static_cast<int64_t>(y) * frame_stride + x, c);
 }
 
 constexpr unsigned NOISE_MAX_BLOCKS = 512;   // workgroups of the noise kernel: each sends one set of atomics
@@ -168,37 +157,15 @@ __global__ __launch_bounds__(256) void rt4_light_noise_kernel(const rt4_light_px
   }
 }
 
-int light_check_image(const void* p, int64_t stride, int32_t w, const char* what, size_t align, char* err, size_t errlen) {
-  if (stride < w) return rt4_set_err(err, errlen, "%s: row stride smaller than width", what), RT4_ERR_ARG;
-  if (reinterpret_cast<uintptr_t>(p) % align != 0)
-    return rt4_set_err(err, errlen, "%s not aligned to %zu bytes", what, align), RT4_ERR_ARG;
-  return RT4_OK;
+PostImage light_image(const rt4_light_px* p, int64_t stride, int32_t w, int32_t h) {
+  return post_image(p, stride, w, h, sizeof(rt4_light_px), "light accumulator");
 }
 
-// Host staging of the _host variants: a device copy of a strided host image (the padding keeps its bytes on the way
-// back because it made the way there).
-struct LightStage {
-  void* d = nullptr;
-  size_t bytes = 0;
-  hipError_t up(const void* host, size_t n) {
-    bytes = n;
-    hipError_t e = hipMalloc(&d, n);
-    if (e == hipSuccess && host) e = hipMemcpy(d, host, n, hipMemcpyHostToDevice);
-    return e;
-  }
-  hipError_t down(void* host) const { return hipMemcpy(host, d, bytes, hipMemcpyDeviceToHost); }
-  ~LightStage() {
-    if (d) (void)hipFree(d);
-  }
-};
-
-}  // namespace
-
-extern "C" {
-
-int rt4_render_light_device(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, const rt4_region* region,
-                            rt4_light_px* d_light, int64_t row_stride_px, unsigned long long* d_counter, void* stream,
-                            char* err, size_t errlen) {
+// rt4_render_light_device, and with a tile list rt4_render_light_tiles_device (rt4_light_tiles.h): the checks, then the
+// frames in launches of rt4_context_frames_per_launch.
+int render_light(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, const rt4_region* region, const TileList* tl,
+                 rt4_light_px* d_light, int64_t row_stride_px, unsigned long long* d_counter, void* stream, char* err,
+                 size_t errlen) {
   if (!ctx || !u || !region || !d_light) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
   if (n_frames < 1) return rt4_set_err(err, errlen, "n_frames %d < 1", n_frames), RT4_ERR_ARG;
   if (region->w > 8191 || region->h > 8191)
@@ -212,6 +179,17 @@ int rt4_render_light_device(rt4_context* ctx, const rt4_uniforms* u, int32_t n_f
     x.part = u[0].part;
     if (std::memcmp(&x, &u[0], sizeof x) != 0)
       return rt4_set_err(err, errlen, "frame %d: uniforms other than seed/part differ from frame 0", f), RT4_ERR_ARG;
+  }
+  if (tl) {  // an empty list returns below without a launch: what launch_jobs would refuse is refused here first
+    const int st = rt4_check_render_args(u, region, row_stride_px, err, errlen);
+    if (st != RT4_OK) return st;
+    if (!ctx->has_scene) return rt4_set_err(err, errlen, "context has no scene (rt4_context_set_scene)"), RT4_ERR_ARG;
+    const int64_t tiles = static_cast<int64_t>((region->w + 7) / 8) * ((region->h + 7) / 8);
+    if (tl->n < 0 || tl->n > tiles)
+      return rt4_set_err(err, errlen, "n_tiles %d not in [0, %lld]", tl->n, static_cast<long long>(tiles)), RT4_ERR_ARG;
+    if (tl->n > 0 && (!tl->d_tiles || reinterpret_cast<uintptr_t>(tl->d_tiles) % 4u != 0))
+      return rt4_set_err(err, errlen, "tile list NULL or not 4-byte aligned"), RT4_ERR_ARG;
+    if (tl->n == 0) return RT4_OK;
   }
   rt4_section_job job;
   job.region = *region;
@@ -230,28 +208,27 @@ int rt4_render_light_device(rt4_context* ctx, const rt4_uniforms* u, int32_t n_f
       parts[f] = 1.0f;
     }
     const FramePlan fp{n, seeds, parts};
-    const int st = launch_jobs(ctx, &job, 1, RT4_FRAME_RGBA32F, d_counter, stream, err, errlen, &fp, &lt);
+    const int st = launch_jobs(ctx, &job, 1, RT4_FRAME_RGBA32F, d_counter, stream, err, errlen, &fp, &lt, tl);
     if (st != RT4_OK) return st;
   }
   return RT4_OK;
 }
 
-int rt4_render_light_host(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, const rt4_region* region,
-                          rt4_light_px* light, int64_t row_stride_px, uint64_t* n_intersections, char* err, size_t errlen) {
-  if (!ctx || !u || !region || !light) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
-  if (n_frames < 1) return rt4_set_err(err, errlen, "n_frames %d < 1", n_frames), RT4_ERR_ARG;
-  int st = rt4_check_render_args(u, region, row_stride_px, err, errlen);
-  if (st != RT4_OK) return st;
-  if (n_intersections) *n_intersections = 0;
-  if (region->w == 0 || region->h == 0) return RT4_OK;
+// The staging of rt4_render_light_host and rt4_render_light_tiles_host behind their own argument checks: the
+// accumulator both ways, a zeroed counter, and the tile list when there is one (`listed`; it may be empty).
+int render_light_staged(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, const rt4_region* region, bool listed,
+                        const uint32_t* tiles, int32_t n_tiles, rt4_light_px* light, int64_t row_stride_px,
+                        uint64_t* n_intersections, const char* what, char* err, size_t errlen) {
   HIP_TRY(hipSetDevice(ctx->device));
-  LightStage acc, cnt;
+  HostStage acc, cnt, lst;
   hipError_t e = acc.up(light, image_span(row_stride_px, region->w, region->h) * sizeof(rt4_light_px));
   if (e == hipSuccess) e = cnt.up(nullptr, sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMemset(cnt.d, 0, sizeof(unsigned long long));
+  if (e == hipSuccess && listed && n_tiles > 0) e = lst.up(tiles, static_cast<size_t>(n_tiles) * sizeof(uint32_t));
   if (e == hipSuccess) {
-    st = rt4_render_light_device(ctx, u, n_frames, region, static_cast<rt4_light_px*>(acc.d), row_stride_px,
-                                 static_cast<unsigned long long*>(cnt.d), nullptr, err, errlen);
+    const TileList tl{lst.as<const uint32_t>(), n_tiles};
+    const int st = render_light(ctx, u, n_frames, region, listed ? &tl : nullptr, acc.as<rt4_light_px>(), row_stride_px,
+                                cnt.as<unsigned long long>(), nullptr, err, errlen);
     if (st != RT4_OK) return st;
     e = hipDeviceSynchronize();
     unsigned long long c = 0;
@@ -259,8 +236,30 @@ int rt4_render_light_host(rt4_context* ctx, const rt4_uniforms* u, int32_t n_fra
     if (e == hipSuccess) e = hipMemcpy(&c, cnt.d, sizeof c, hipMemcpyDeviceToHost);
     if (e == hipSuccess && n_intersections) *n_intersections = c;
   }
-  if (e != hipSuccess) return rt4_set_err(err, errlen, "render_light_host failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
+  if (e != hipSuccess) return rt4_set_err(err, errlen, "%s failed: %s", what, hipGetErrorString(e)), RT4_ERR_HIP;
   return RT4_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt4_render_light_device(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, const rt4_region* region,
+                            rt4_light_px* d_light, int64_t row_stride_px, unsigned long long* d_counter, void* stream,
+                            char* err, size_t errlen) {
+  return render_light(ctx, u, n_frames, region, nullptr, d_light, row_stride_px, d_counter, stream, err, errlen);
+}
+
+int rt4_render_light_host(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, const rt4_region* region,
+                          rt4_light_px* light, int64_t row_stride_px, uint64_t* n_intersections, char* err, size_t errlen) {
+  if (!ctx || !u || !region || !light) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
+  if (n_frames < 1) return rt4_set_err(err, errlen, "n_frames %d < 1", n_frames), RT4_ERR_ARG;
+  const int st = rt4_check_render_args(u, region, row_stride_px, err, errlen);
+  if (st != RT4_OK) return st;
+  if (n_intersections) *n_intersections = 0;
+  if (region->w == 0 || region->h == 0) return RT4_OK;
+  return render_light_staged(ctx, u, n_frames, region, false, nullptr, 0, light, row_stride_px, n_intersections,
+                             "render_light_host", err, errlen);
 }
 
 int rt4_light_resolve_device(rt4_context* ctx, const rt4_light_px* d_light, int64_t light_stride, float k, void* d_frame,
@@ -271,25 +270,16 @@ int rt4_light_resolve_device(rt4_context* ctx, const rt4_light_px* d_light, int6
   if (px_bytes == 0) return rt4_set_err(err, errlen, "unknown frame format %d", format), RT4_ERR_ARG;
   if (w <= 0 || h <= 0 || w > 65535 || h > 65535)
     return rt4_set_err(err, errlen, "image size %d x %d not in [1, 65535]", w, h), RT4_ERR_ARG;
-  int st = light_check_image(d_light, light_stride, w, "light accumulator", 16u, err, errlen);
-  if (st == RT4_OK) st = light_check_image(d_frame, frame_stride, w, "frame", static_cast<size_t>(px_bytes), err, errlen);
+  const PostImage in = light_image(d_light, light_stride, w, h);
+  const PostImage out = post_image(d_frame, frame_stride, w, h, static_cast<size_t>(px_bytes), "frame");
+  const int st = post_check_args(&out, 1, &in, 1, err, errlen);
   if (st != RT4_OK) return st;
-  if (rp_overlap(rp_span(d_light, light_stride, w, h, sizeof(rt4_light_px)),
-                 rp_span(d_frame, frame_stride, w, h, static_cast<size_t>(px_bytes))))
-    return rt4_set_err(err, errlen, "the frame overlaps the light accumulator"), RT4_ERR_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int rc = order_launch(ctx, s, err, errlen);
-  if (rc != RT4_OK) return rc;
-  const dim3 grid(static_cast<unsigned>((w + LT_BX - 1) / LT_BX), static_cast<unsigned>((h + LT_BY - 1) / LT_BY)), block(256);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(rt4_light_resolve_kernel, grid, block, 0, s, d_light, light_stride, k, d_frame, format, frame_stride, w, h);
-  const hipError_t le = hipGetLastError();
-  rc = done_launch(ctx, s, err, errlen);
-  if (le != hipSuccess) {
-    rt4_set_err(err, errlen, "light resolve kernel launch failed: %s", hipGetErrorString(le));
-    return RT4_ERR_HIP;
-  }
-  return rc;
+  return post_launch(ctx, s, "light resolve kernel", err, errlen, [&] {
+    hipLaunchKernelGGL(rt4_light_resolve_kernel, px_grid(w, h), dim3(256), 0, s, d_light, light_stride, k, d_frame, format,
+                       frame_stride, w, h);
+    return hipGetLastError();
+  });
 }
 
 int rt4_light_resolve_host(rt4_context* ctx, const rt4_light_px* light, int64_t light_stride, float k, void* frame,
@@ -300,12 +290,12 @@ int rt4_light_resolve_host(rt4_context* ctx, const rt4_light_px* light, int64_t 
   if (w <= 0 || h <= 0 || light_stride < w || frame_stride < w)
     return rt4_set_err(err, errlen, "bad image size or row stride"), RT4_ERR_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
-  LightStage acc, out;
+  HostStage acc, out;
   hipError_t e = acc.up(light, image_span(light_stride, w, h) * sizeof(rt4_light_px));
   if (e == hipSuccess) e = out.up(frame, image_span(frame_stride, w, h) * static_cast<size_t>(px_bytes));
   if (e == hipSuccess) {
-    const int st = rt4_light_resolve_device(ctx, static_cast<const rt4_light_px*>(acc.d), light_stride, k, out.d, format,
-                                            frame_stride, w, h, nullptr, err, errlen);
+    const int st = rt4_light_resolve_device(ctx, acc.as<const rt4_light_px>(), light_stride, k, out.d, format, frame_stride, w,
+                                            h, nullptr, err, errlen);
     if (st != RT4_OK) return st;
     e = hipDeviceSynchronize();
     if (e == hipSuccess) e = out.down(frame);
@@ -320,46 +310,31 @@ int rt4_light_noise_device(rt4_context* ctx, const rt4_light_px* d_light, int64_
   if (!ctx || !d_light || !d_stats) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
   if (w <= 0 || h <= 0 || w > 65535 || h > 65535)
     return rt4_set_err(err, errlen, "image size %d x %d not in [1, 65535]", w, h), RT4_ERR_ARG;
-  int st = light_check_image(d_light, light_stride, w, "light accumulator", 16u, err, errlen);
-  if (st == RT4_OK && d_se) st = light_check_image(d_se, map_stride, w, "se map", 4u, err, errlen);
-  if (st == RT4_OK && d_q) st = light_check_image(d_q, map_stride, w, "q map", 4u, err, errlen);
-  if (st != RT4_OK) return st;
-  if (reinterpret_cast<uintptr_t>(d_tile_above) % 4u != 0 || reinterpret_cast<uintptr_t>(d_stats) % 8u != 0)
-    return rt4_set_err(err, errlen, "tile image or statistics not aligned"), RT4_ERR_ARG;
   const int32_t tx = (w + 7) / 8, ty = (h + 7) / 8;
-  const RpSpan in = rp_span(d_light, light_stride, w, h, sizeof(rt4_light_px));
-  RpSpan outs[4];
-  int n_out = 0;
-  outs[n_out++] = rp_span(d_stats, 1, 1, 1, sizeof(rt4_noise_stats));
-  if (d_se) outs[n_out++] = rp_span(d_se, map_stride, w, h, sizeof(float));
-  if (d_q) outs[n_out++] = rp_span(d_q, map_stride, w, h, sizeof(float));
-  if (d_tile_above) outs[n_out++] = rp_span(d_tile_above, tx, tx, ty, sizeof(int32_t));
-  for (int a = 0; a < n_out; a++) {
-    if (rp_overlap(outs[a], in)) return rt4_set_err(err, errlen, "an output overlaps the light accumulator"), RT4_ERR_ARG;
-    for (int b = a + 1; b < n_out; b++)
-      if (rp_overlap(outs[a], outs[b])) return rt4_set_err(err, errlen, "two outputs overlap"), RT4_ERR_ARG;
-  }
+  const PostImage in = light_image(d_light, light_stride, w, h);
+  PostImage outs[4];
+  size_t n_out = 0;
+  outs[n_out++] = PostImage{d_stats, 1, 1, 1, sizeof(rt4_noise_stats), 8u, "statistics"};
+  if (d_se) outs[n_out++] = post_image(d_se, map_stride, w, h, sizeof(float), "se map");
+  if (d_q) outs[n_out++] = post_image(d_q, map_stride, w, h, sizeof(float), "q map");
+  if (d_tile_above) outs[n_out++] = post_image(d_tile_above, tx, tx, ty, sizeof(int32_t), "tile image");
+  const int st = post_check_args(outs, n_out, &in, 1, err, errlen);
+  if (st != RT4_OK) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int rc = order_launch(ctx, s, err, errlen);
-  if (rc != RT4_OK) return rc;
-  // the statistics start from zero on every call; pixels (< 2^32) is the host's: its low word, after the zeroes
-  hipError_t le = hipMemsetAsync(d_stats, 0, sizeof(rt4_noise_stats), s);
-  if (le == hipSuccess)
-    le = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&d_stats->pixels),
-                           static_cast<int>(static_cast<uint32_t>(w) * static_cast<uint32_t>(h)), 1, s);
-  if (le == hipSuccess) {
-    const unsigned tiles = static_cast<unsigned>(tx) * static_cast<unsigned>(ty);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(rt4_light_noise_kernel, dim3(std::min((tiles + 3u) / 4u, NOISE_MAX_BLOCKS)), dim3(256), 0, s, d_light, light_stride, w, h, k, threshold,
-                       d_se, d_q, map_stride, d_tile_above, d_stats);
-    le = hipGetLastError();
-  }
-  rc = done_launch(ctx, s, err, errlen);
-  if (le != hipSuccess) {
-    rt4_set_err(err, errlen, "light noise launch failed: %s", hipGetErrorString(le));
-    return RT4_ERR_HIP;
-  }
-  return rc;
+  return post_launch(ctx, s, "light noise", err, errlen, [&] {
+    // the statistics start from zero on every call; pixels (< 2^32) is the host's: its low word, after the zeroes
+    hipError_t le = hipMemsetAsync(d_stats, 0, sizeof(rt4_noise_stats), s);
+    if (le == hipSuccess)
+      le = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&d_stats->pixels),
+                             static_cast<int>(static_cast<uint32_t>(w) * static_cast<uint32_t>(h)), 1, s);
+    if (le == hipSuccess) {
+      const unsigned tiles = static_cast<unsigned>(tx) * static_cast<unsigned>(ty);
+      hipLaunchKernelGGL(rt4_light_noise_kernel, dim3(std::min((tiles + 3u) / 4u, NOISE_MAX_BLOCKS)), dim3(256), 0, s, d_light,
+                         light_stride, w, h, k, threshold, d_se, d_q, map_stride, d_tile_above, d_stats);
+      le = hipGetLastError();
+    }
+    return le;
+  });
 }
 
 int rt4_light_noise_host(rt4_context* ctx, const rt4_light_px* light, int64_t light_stride, int32_t w, int32_t h, float k,
@@ -369,7 +344,7 @@ int rt4_light_noise_host(rt4_context* ctx, const rt4_light_px* light, int64_t li
   if (w <= 0 || h <= 0 || light_stride < w || ((se || q) && map_stride < w))
     return rt4_set_err(err, errlen, "bad image size or row stride"), RT4_ERR_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
-  LightStage acc, dse, dq, dt, ds;
+  HostStage acc, dse, dq, dt, ds;
   const size_t map_bytes = (se || q) ? image_span(map_stride, w, h) * sizeof(float) : 0;
   const size_t tile_bytes = static_cast<size_t>((w + 7) / 8) * static_cast<size_t>((h + 7) / 8) * sizeof(int32_t);
   hipError_t e = acc.up(light, image_span(light_stride, w, h) * sizeof(rt4_light_px));
@@ -378,9 +353,9 @@ int rt4_light_noise_host(rt4_context* ctx, const rt4_light_px* light, int64_t li
   if (e == hipSuccess && tile_above) e = dt.up(tile_above, tile_bytes);
   if (e == hipSuccess) e = ds.up(stats, sizeof(rt4_noise_stats));
   if (e == hipSuccess) {
-    const int st = rt4_light_noise_device(ctx, static_cast<const rt4_light_px*>(acc.d), light_stride, w, h, k, threshold,
-                                          static_cast<float*>(dse.d), static_cast<float*>(dq.d), map_stride,
-                                          static_cast<int32_t*>(dt.d), static_cast<rt4_noise_stats*>(ds.d), nullptr, err, errlen);
+    const int st = rt4_light_noise_device(ctx, acc.as<const rt4_light_px>(), light_stride, w, h, k, threshold, dse.as<float>(),
+                                          dq.as<float>(), map_stride, dt.as<int32_t>(), ds.as<rt4_noise_stats>(), nullptr,
+                                          err, errlen);
     if (st != RT4_OK) return st;
     e = hipDeviceSynchronize();
     if (e == hipSuccess && se) e = dse.down(se);

@@ -1,7 +1,7 @@
 // rt4_light_denoise.h — the variance-guided a-trous filter of a light accumulator of rt4.h (rt4_light_denoise_device;
-// DESIGN.md §4.38): kernels and entry points. Part of rt4_trace.hip's translation unit (included at its end, after
-// rt4_light.h: the context, the blend_* store helpers, the launch ordering, rp_span / rp_overlap, light_tone,
-// light_check_image and LightStage live there); no other kernel uses anything from here.
+// DESIGN.md §4.38): kernels and entry points. From rt4_post.h: the argument checks, the launch bracket, the pixel grid,
+// px_store_opaque, HostStage and grow_scratch; from rt4_light.h: light_tone and light_image. No other kernel uses
+// anything from here.
 //
 // One call, in the shape of rt4_denoise.h: a pack pass builds level 0 (the state: {L, Y} 16 B and V 4 B) and the guide
 // (normal 16 B; {id, depth} 8 B with id = the surface of a filterable pixel, else -1), then one pass per level between
@@ -17,9 +17,8 @@
 
 namespace {
 
-constexpr int LD_BX = 32, LD_BY = 8;                    // pixels per workgroup (one lane each)
 constexpr int LD_MAX_TILED_STEP = 2;                    // strides staged in LDS
-constexpr int LD_TILE_MAX = (LD_BX + 4 * LD_MAX_TILED_STEP) * (LD_BY + 4 * LD_MAX_TILED_STEP);  // 40 x 16 pixels
+constexpr int LD_TILE_MAX = (PX_BX + 4 * LD_MAX_TILED_STEP) * (PX_BY + 4 * LD_MAX_TILED_STEP);  // 40 x 16 pixels
 constexpr size_t LD_SCRATCH_PX_BYTES = 64;              // 2 x (16 + 4) state, 16 + 8 guide
 
 struct LdArgs {
@@ -45,33 +44,20 @@ __device__ __forceinline__ float ld_variance0(float m2, int32_t n) {
   return (m2 / static_cast<float>(n - 1)) / static_cast<float>(n);
 }
 
-// A colour through the store rule of the format, alpha 1 (rt4_light_resolve_kernel does the same).
-__device__ __forceinline__ void ld_store(void* frame, int32_t format, int64_t at, V3 c) {
-  if (format == RT4_FRAME_RGBA16F) {
-    h4v zero;
-    zero[0] = zero[1] = zero[2] = zero[3] = static_cast<_Float16>(0.0f);
-    reinterpret_cast<h4v*>(frame)[at] = blend_f16(c, 1.0f, zero);
-  } else if (format == RT4_FRAME_RGBA8) {
-    reinterpret_cast<uint32_t*>(frame)[at] = blend_u8(c, 1.0f, 0u);
-  } else {
-    reinterpret_cast<float4*>(frame)[at] = blend_f32(c, 1.0f, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-  }
-}
-
 // levels = 0: rt4_light_resolve_kernel's frame, and {mean, n >= 2 ? V_0 : +inf} into filtered. The G-buffer plays no
 // part: a filterable pixel has n >= 2, and its L_0 and V_0 are these.
 __global__ __launch_bounds__(256) void rt4_light_denoise_level0_kernel(const rt4_light_px* __restrict__ light, int64_t light_stride,
                                                                        float k, void* __restrict__ frame, int32_t format,
                                                                        int64_t frame_stride, float4* __restrict__ filtered,
                                                                        int64_t filtered_stride, int32_t w, int32_t h) {
-  const int x = static_cast<int>(blockIdx.x) * LD_BX + static_cast<int>(threadIdx.x & 31u);
-  const int y = static_cast<int>(blockIdx.y) * LD_BY + static_cast<int>(threadIdx.x >> 5);
+  const int2 xy = px_xy();
+  const int x = xy.x, y = xy.y;
   if (x >= w || y >= h) return;
   const float4* st = reinterpret_cast<const float4*>(light + static_cast<int64_t>(y) * light_stride + x);
   const float4 m = st[0], t = st[1];
   const int32_t n = __float_as_int(t.y);
   const V3 c = n == 0 ? V3{0.0f, 0.0f, 0.0f} : V3{light_tone(k, m.x), light_tone(k, m.y), light_tone(k, m.z)};
-  ld_store(frame, format, static_cast<int64_t>(y) * frame_stride + x, c);
+  px_store_opaque(frame, format, static_cast<int64_t>(y) * frame_stride + x, c);
   if (filtered)
     filtered[static_cast<int64_t>(y) * filtered_stride + x] =
         make_float4(m.x, m.y, m.z, n >= 2 ? ld_variance0(t.x, n) : __builtin_inff());
@@ -83,8 +69,8 @@ __global__ __launch_bounds__(256) void rt4_light_denoise_pack_kernel(const rt4_l
                                                                      int32_t w, int32_t h, float max_refl_prob,
                                                                      float4* __restrict__ s0, float* __restrict__ v0,
                                                                      float4* __restrict__ gn, int2* __restrict__ gi) {
-  const int x = static_cast<int>(blockIdx.x) * LD_BX + static_cast<int>(threadIdx.x & 31u);
-  const int y = static_cast<int>(blockIdx.y) * LD_BY + static_cast<int>(threadIdx.x >> 5);
+  const int2 xy = px_xy();
+  const int x = xy.x, y = xy.y;
   if (x >= w || y >= h) return;
   const float4* st = reinterpret_cast<const float4*>(light + static_cast<int64_t>(y) * light_stride + x);
   const float4 m = st[0], t = st[1];  // m: mean rgb, mean_y; t: m2, n
@@ -111,12 +97,12 @@ __global__ __launch_bounds__(256) void rt4_light_denoise_level_kernel(const LdAr
   __shared__ float l_nx[LN], l_ny[LN], l_nz[LN], l_nw[LN], l_z[LN];
   __shared__ int l_id[LN];
   const int tx = static_cast<int>(threadIdx.x & 31u), ty = static_cast<int>(threadIdx.x >> 5);
-  const int ox = static_cast<int>(blockIdx.x) * LD_BX, oy = static_cast<int>(blockIdx.y) * LD_BY;
+  const int ox = static_cast<int>(blockIdx.x) * PX_BX, oy = static_cast<int>(blockIdx.y) * PX_BY;
   const int x = ox + tx, y = oy + ty;
   const int s = a.step, w = a.w, h = a.h;
-  const int R = 2 * s, T = LD_BX + 2 * R;  // halo, LDS row pitch (TILED)
+  const int R = 2 * s, T = PX_BX + 2 * R;  // halo, LDS row pitch (TILED)
   if (TILED) {
-    const int n = T * (LD_BY + 2 * R);  // <= LD_TILE_MAX: the host launches this instantiation for s <= 2 only
+    const int n = T * (PX_BY + 2 * R);  // <= LD_TILE_MAX: the host launches this instantiation for s <= 2 only
     for (int k = static_cast<int>(threadIdx.x); k < n; k += 256) {
       const int ly = k / T, lx = k - ly * T;
       const int gx = ox - R + lx, gy = oy - R + ly;
@@ -255,7 +241,7 @@ __global__ __launch_bounds__(256) void rt4_light_denoise_level_kernel(const LdAr
   if (idp < 0)
     empty = reinterpret_cast<const int32_t*>(a.light + static_cast<int64_t>(y) * a.light_stride + x)[5] == 0;
   const V3 c = empty ? V3{0.0f, 0.0f, 0.0f} : V3{light_tone(a.k, cr), light_tone(a.k, cg), light_tone(a.k, cb)};
-  ld_store(a.frame, a.format, static_cast<int64_t>(y) * a.frame_stride + x, c);
+  px_store_opaque(a.frame, a.format, static_cast<int64_t>(y) * a.frame_stride + x, c);
   if (a.filtered) a.filtered[static_cast<int64_t>(y) * a.filtered_stride + x] = make_float4(cr, cg, cb, cv);
 }
 
@@ -264,7 +250,7 @@ __global__ __launch_bounds__(256) void rt4_light_denoise_level_kernel(const LdAr
 extern "C" {
 
 uint64_t rt4_context_light_denoise_bytes(const rt4_context* ctx) {
-  return ctx ? static_cast<uint64_t>(ctx->light_denoise_px) * LD_SCRATCH_PX_BYTES : 0u;
+  return ctx ? static_cast<uint64_t>(ctx->light_denoise.cap) * LD_SCRATCH_PX_BYTES : 0u;
 }
 
 int rt4_light_denoise_device(rt4_context* ctx, const rt4_light_px* d_light, int64_t light_stride,
@@ -277,90 +263,69 @@ int rt4_light_denoise_device(rt4_context* ctx, const rt4_light_px* d_light, int6
   if (px_bytes == 0) return rt4_set_err(err, errlen, "unknown frame format %d", format), RT4_ERR_ARG;
   if (w <= 0 || h <= 0 || w > 65535 || h > 65535)
     return rt4_set_err(err, errlen, "image size %d x %d not in [1, 65535]", w, h), RT4_ERR_ARG;
-  int st = light_check_image(d_light, light_stride, w, "light accumulator", 16u, err, errlen);
-  if (st == RT4_OK) st = light_check_image(d_gbuf, gbuf_stride, w, "G-buffer", 16u, err, errlen);
-  if (st == RT4_OK) st = light_check_image(d_frame, frame_stride, w, "frame", static_cast<size_t>(px_bytes), err, errlen);
-  if (st == RT4_OK && d_filtered) st = light_check_image(d_filtered, filtered_stride, w, "filtered light", 16u, err, errlen);
+  const PostImage in[2] = {light_image(d_light, light_stride, w, h),
+                           post_image(d_gbuf, gbuf_stride, w, h, sizeof(rt4_gbuffer_px), "G-buffer")};
+  const PostImage out[2] = {post_image(d_frame, frame_stride, w, h, static_cast<size_t>(px_bytes), "frame"),
+                            post_image(d_filtered, filtered_stride, w, h, 16u, "filtered light")};
+  int st = post_check_args(out, d_filtered ? 2 : 1, in, 2, err, errlen);
   if (st != RT4_OK) return st;
   if (params->levels < 0 || params->levels > RT4_LIGHT_DENOISE_MAX_LEVELS)
     return rt4_set_err(err, errlen, "levels %d not in [0, %d]", params->levels, RT4_LIGHT_DENOISE_MAX_LEVELS), RT4_ERR_ARG;
   if (!(params->sigma >= 0.0f) || !(params->eps >= 0.0f))  // negative or NaN
     return rt4_set_err(err, errlen, "sigma and eps must be >= 0"), RT4_ERR_ARG;
-  const RpSpan in[2] = {rp_span(d_light, light_stride, w, h, sizeof(rt4_light_px)),
-                        rp_span(d_gbuf, gbuf_stride, w, h, sizeof(rt4_gbuffer_px))};
-  RpSpan out[2];
-  int n_out = 0;
-  out[n_out++] = rp_span(d_frame, frame_stride, w, h, static_cast<size_t>(px_bytes));
-  if (d_filtered) out[n_out++] = rp_span(d_filtered, filtered_stride, w, h, 16u);
-  if (n_out == 2 && rp_overlap(out[0], out[1])) return rt4_set_err(err, errlen, "the two outputs overlap"), RT4_ERR_ARG;
-  for (int o = 0; o < n_out; o++)
-    for (const RpSpan& i : in)
-      if (rp_overlap(out[o], i)) return rt4_set_err(err, errlen, "an output overlaps an input"), RT4_ERR_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const size_t npx = static_cast<size_t>(w) * static_cast<size_t>(h);
   const int32_t levels = params->levels;
-  if (levels > 0 && ctx->light_denoise_px < npx) {  // a larger image than any before: wait for the launches in flight, grow once
-    HIP_TRY(hipStreamSynchronize(s));
-    if (ctx->launched) HIP_TRY(hipEventSynchronize(ctx->done));
-    if (ctx->d_light_denoise) (void)hipFree(ctx->d_light_denoise);
-    ctx->d_light_denoise = nullptr;
-    ctx->light_denoise_px = 0;
-    HIP_TRY(hipMalloc(&ctx->d_light_denoise, npx * LD_SCRATCH_PX_BYTES));
-    ctx->light_denoise_px = npx;
+  if (levels > 0) {  // a larger image than any before grows the scratch once
+    st = grow_scratch(ctx, ctx->light_denoise, s, static_cast<size_t>(w) * static_cast<size_t>(h), LD_SCRATCH_PX_BYTES, err, errlen);
+    if (st != RT4_OK) return st;
   }
   // the six arrays of the scratch, each for the context's largest image (offsets are multiples of their alignment)
-  char* base = static_cast<char*>(ctx->d_light_denoise);
-  const size_t cap = ctx->light_denoise_px;
+  char* base = static_cast<char*>(ctx->light_denoise.d);
+  const size_t cap = ctx->light_denoise.cap;
   float4* level[2] = {reinterpret_cast<float4*>(base), reinterpret_cast<float4*>(base + cap * 16u)};
   float4* gn = reinterpret_cast<float4*>(base + cap * 32u);
   int2* gi = reinterpret_cast<int2*>(base + cap * 48u);
   float* level_v[2] = {reinterpret_cast<float*>(base + cap * 56u), reinterpret_cast<float*>(base + cap * 60u)};
-  int rc = order_launch(ctx, s, err, errlen);
-  if (rc != RT4_OK) return rc;
-  const dim3 grid(static_cast<unsigned>((w + LD_BX - 1) / LD_BX), static_cast<unsigned>((h + LD_BY - 1) / LD_BY)), block(256);
-  float4* filtered = reinterpret_cast<float4*>(d_filtered);
-  (void)hipGetLastError();
-  if (levels == 0)
-    hipLaunchKernelGGL(rt4_light_denoise_level0_kernel, grid, block, 0, s, d_light, light_stride, k, d_frame, format,
-                       frame_stride, filtered, filtered_stride, w, h);
-  else
-    hipLaunchKernelGGL(rt4_light_denoise_pack_kernel, grid, block, 0, s, d_light, light_stride, d_gbuf, gbuf_stride, w, h,
-                       params->max_refl_prob, level[0], level_v[0], gn, gi);
-  hipError_t le = hipGetLastError();
-  for (int32_t l = 0; l < levels && le == hipSuccess; l++) {
-    const bool last = l + 1 == levels;
-    LdArgs a;
-    a.w = w;
-    a.h = h;
-    a.step = 1 << l;
-    a.cos_min = params->cos_min;
-    a.depth_tol = params->depth_tol;
-    a.sigma = params->sigma;
-    a.eps = params->eps;
-    a.k = k;
-    a.src = level[l & 1];
-    a.src_v = level_v[l & 1];
-    a.gn = gn;
-    a.gi = gi;
-    a.dst = last ? nullptr : level[(l + 1) & 1];
-    a.dst_v = last ? nullptr : level_v[(l + 1) & 1];
-    a.light = d_light;
-    a.light_stride = light_stride;
-    a.frame = d_frame;
-    a.frame_stride = frame_stride;
-    a.format = format;
-    a.filtered = filtered;
-    a.filtered_stride = filtered_stride;
-    if (a.step <= LD_MAX_TILED_STEP) hipLaunchKernelGGL(rt4_light_denoise_level_kernel<true>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(rt4_light_denoise_level_kernel<false>, grid, block, 0, s, a);
-    le = hipGetLastError();
-  }
-  rc = done_launch(ctx, s, err, errlen);
-  if (le != hipSuccess) {
-    rt4_set_err(err, errlen, "light denoise kernel launch failed: %s", hipGetErrorString(le));
-    return RT4_ERR_HIP;
-  }
-  return rc;
+  return post_launch(ctx, s, "light denoise kernel", err, errlen, [&] {
+    const dim3 grid = px_grid(w, h), block(256);
+    float4* filtered = reinterpret_cast<float4*>(d_filtered);
+    if (levels == 0)
+      hipLaunchKernelGGL(rt4_light_denoise_level0_kernel, grid, block, 0, s, d_light, light_stride, k, d_frame, format,
+                         frame_stride, filtered, filtered_stride, w, h);
+    else
+      hipLaunchKernelGGL(rt4_light_denoise_pack_kernel, grid, block, 0, s, d_light, light_stride, d_gbuf, gbuf_stride, w, h,
+                         params->max_refl_prob, level[0], level_v[0], gn, gi);
+    hipError_t le = hipGetLastError();
+    for (int32_t l = 0; l < levels && le == hipSuccess; l++) {
+      const bool last = l + 1 == levels;
+      LdArgs a;
+      a.w = w;
+      a.h = h;
+      a.step = 1 << l;
+      a.cos_min = params->cos_min;
+      a.depth_tol = params->depth_tol;
+      a.sigma = params->sigma;
+      a.eps = params->eps;
+      a.k = k;
+      a.src = level[l & 1];
+      a.src_v = level_v[l & 1];
+      a.gn = gn;
+      a.gi = gi;
+      a.dst = last ? nullptr : level[(l + 1) & 1];
+      a.dst_v = last ? nullptr : level_v[(l + 1) & 1];
+      a.light = d_light;
+      a.light_stride = light_stride;
+      a.frame = d_frame;
+      a.frame_stride = frame_stride;
+      a.format = format;
+      a.filtered = filtered;
+      a.filtered_stride = filtered_stride;
+      if (a.step <= LD_MAX_TILED_STEP) hipLaunchKernelGGL(rt4_light_denoise_level_kernel<true>, grid, block, 0, s, a);
+      else hipLaunchKernelGGL(rt4_light_denoise_level_kernel<false>, grid, block, 0, s, a);
+      le = hipGetLastError();
+    }
+    return le;
+  });
 }
 
 int rt4_light_denoise_host(rt4_context* ctx, const rt4_light_px* light, int64_t light_stride, const rt4_gbuffer_px* gbuf,
@@ -373,16 +338,15 @@ int rt4_light_denoise_host(rt4_context* ctx, const rt4_light_px* light, int64_t 
   if (w <= 0 || h <= 0 || light_stride < w || gbuf_stride < w || frame_stride < w || (filtered && filtered_stride < w))
     return rt4_set_err(err, errlen, "bad image size or row stride"), RT4_ERR_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
-  LightStage acc, g, out, fl;
+  HostStage acc, g, out, fl;
   hipError_t e = acc.up(light, image_span(light_stride, w, h) * sizeof(rt4_light_px));
   if (e == hipSuccess) e = g.up(gbuf, image_span(gbuf_stride, w, h) * sizeof(rt4_gbuffer_px));
   if (e == hipSuccess) e = out.up(frame, image_span(frame_stride, w, h) * static_cast<size_t>(px_bytes));
   if (e == hipSuccess && filtered) e = fl.up(filtered, image_span(filtered_stride, w, h) * 16u);
   if (e == hipSuccess) {
-    const int st = rt4_light_denoise_device(ctx, static_cast<const rt4_light_px*>(acc.d), light_stride,
-                                            static_cast<const rt4_gbuffer_px*>(g.d), gbuf_stride, k, params, out.d, format,
-                                            frame_stride, static_cast<float*>(fl.d), filtered_stride, w, h, nullptr, err,
-                                            errlen);
+    const int st = rt4_light_denoise_device(ctx, acc.as<const rt4_light_px>(), light_stride, g.as<const rt4_gbuffer_px>(),
+                                            gbuf_stride, k, params, out.d, format, frame_stride, fl.as<float>(),
+                                            filtered_stride, w, h, nullptr, err, errlen);
     if (st != RT4_OK) return st;
     e = hipDeviceSynchronize();
     if (e == hipSuccess) e = out.down(frame);

@@ -1,8 +1,9 @@
 // rt4_light_tiles.h — adaptive light sampling of rt4.h (rt4_light_select_tiles_device, rt4_render_light_tiles_device;
-// DESIGN.md §4.39): kernels and entry points. Part of rt4_trace.hip's translation unit (included at its end, after
-// rt4_light_denoise.h: light_apply, light_tone, light_check_image, LightStage and LIGHT_LOAD_BATCH come from rt4_light.h,
-// launch_jobs and TileList from rt4_trace.hip); no trace kernel uses anything from here, and none is changed: a tile-list
-// launch hands the trace kernel its list through KernelArgs::order, the way the pre-pass hands it the longest-first order.
+// DESIGN.md §4.39): kernels and entry points. From rt4_post.h: the argument checks, the launch bracket, HostStage and
+// grow_scratch; from rt4_light.h: light_apply, light_tone, LIGHT_LOAD_BATCH, light_image and render_light /
+// render_light_staged (TileList is rt4_trace.hip's). No trace kernel uses anything from here, and none is changed: a
+// tile-list launch hands the trace kernel its list through KernelArgs::order, the way the pre-pass hands it the
+// longest-first order.
 //
 // Selection is two kernels: the flags (a wave per 8x8 tile as in rt4_light_noise_kernel, the hot count one ballot) into
 // context-owned scratch, then one workgroup that walks the tiles in chunks of its size, dilates the flags, and writes
@@ -143,18 +144,19 @@ __global__ __launch_bounds__(256) void rt4_fold_light_tiles_kernel(const KernelA
 
 // launch_jobs with a tile list (rt4_trace.hip): the context's copy of the list holds at least `tiles` entries, followed
 // by the two words {0, 1} the trace kernel reads as KernelArgs::order_ends (a non-zero second word switches its order
-// on). Growing waits for the stream and the context's launches in flight, once per larger region.
+// on): the last two of the scratch's words. Growing waits as grow_scratch does, once per larger region.
 int ensure_tile_list(rt4_context* ctx, unsigned tiles, hipStream_t s, char* err, size_t errlen) {
-  if (ctx->d_tile_list && ctx->tile_list_cap >= tiles) return RT4_OK;
-  HIP_TRY(hipStreamSynchronize(s));
-  if (ctx->launched) HIP_TRY(hipEventSynchronize(ctx->done));
-  if (ctx->d_tile_list) (void)hipFree(ctx->d_tile_list);
-  ctx->d_tile_list = nullptr;
-  ctx->tile_list_cap = 0;
-  HIP_TRY(hipMalloc(&ctx->d_tile_list, (static_cast<size_t>(tiles) + 2) * sizeof(uint32_t)));
+  CtxScratch& tl = ctx->tile_list;
+  const size_t words = static_cast<size_t>(tiles) + 2;
+  if (tl.cap >= words) return RT4_OK;
+  const int st = grow_scratch(ctx, tl, s, words, sizeof(uint32_t), err, errlen);
+  if (st != RT4_OK) return st;
   const uint32_t ends[2] = {0u, 1u};
-  HIP_TRY(hipMemcpy(ctx->d_tile_list + tiles, ends, sizeof ends, hipMemcpyHostToDevice));
-  ctx->tile_list_cap = tiles;
+  const hipError_t e = hipMemcpy(static_cast<uint32_t*>(tl.d) + tiles, ends, sizeof ends, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    tl.cap = 0;  // no list without its end words: the next call grows again
+    return rt4_set_err(err, errlen, "tile list upload failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
+  }
   return RT4_OK;
 }
 
@@ -165,12 +167,12 @@ int stage_tile_list(rt4_context* ctx, const TileList& tl, unsigned tiles, Kernel
   const int st = ensure_tile_list(ctx, tiles, s, err, errlen);
   if (st != RT4_OK) return st;
   const uint32_t n = static_cast<uint32_t>(tl.n);
+  uint32_t* list = static_cast<uint32_t*>(ctx->tile_list.d);
   (void)hipGetLastError();
-  hipLaunchKernelGGL(rt4_tile_list_clamp_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, tl.d_tiles, ctx->d_tile_list, n,
-                     tiles);
+  hipLaunchKernelGGL(rt4_tile_list_clamp_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, tl.d_tiles, list, n, tiles);
   HIP_TRY(hipGetLastError());
-  a.order = ctx->d_tile_list;
-  a.order_ends = ctx->d_tile_list + ctx->tile_list_cap;
+  a.order = list;
+  a.order_ends = list + ctx->tile_list.cap - 2;
   return RT4_OK;
 }
 
@@ -203,8 +205,7 @@ void rt4_tile_select_params_default(rt4_tile_select_params* p) {
 
 uint64_t rt4_context_select_bytes(const rt4_context* ctx) {
   if (!ctx) return 0u;
-  return static_cast<uint64_t>(ctx->select_cap) * sizeof(uint32_t) +
-         (ctx->d_tile_list ? (static_cast<uint64_t>(ctx->tile_list_cap) + 2u) * sizeof(uint32_t) : 0u);
+  return (static_cast<uint64_t>(ctx->select.cap) + static_cast<uint64_t>(ctx->tile_list.cap)) * sizeof(uint32_t);
 }
 
 int rt4_light_select_tiles_device(rt4_context* ctx, const rt4_light_px* d_light, int64_t light_stride, int32_t w, int32_t h,
@@ -213,52 +214,30 @@ int rt4_light_select_tiles_device(rt4_context* ctx, const rt4_light_px* d_light,
   if (!ctx || !d_light || !params || !d_tiles || !d_count) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
   if (w <= 0 || h <= 0 || w > 65535 || h > 65535)
     return rt4_set_err(err, errlen, "image size %d x %d not in [1, 65535]", w, h), RT4_ERR_ARG;
-  int st = light_check_image(d_light, light_stride, w, "light accumulator", 16u, err, errlen);
+  const int32_t tx = (w + 7) / 8, ty = (h + 7) / 8;
+  const PostImage in = light_image(d_light, light_stride, w, h);
+  const PostImage outs[3] = {post_image(d_tiles, tx, tx, ty, sizeof(uint32_t), "tile list"),
+                             post_image(d_count, 1, 1, 1, sizeof(uint32_t), "count"),
+                             post_image(d_tile_state, tx, tx, ty, sizeof(int32_t), "tile state")};
+  int st = post_check_args(outs, d_tile_state ? 3 : 2, &in, 1, err, errlen);
   if (st == RT4_OK) st = select_check_params(params, err, errlen);
   if (st != RT4_OK) return st;
-  if (reinterpret_cast<uintptr_t>(d_tiles) % 4u != 0 || reinterpret_cast<uintptr_t>(d_count) % 4u != 0 ||
-      reinterpret_cast<uintptr_t>(d_tile_state) % 4u != 0)
-    return rt4_set_err(err, errlen, "tile list, count or tile state not aligned"), RT4_ERR_ARG;
-  const int32_t tx = (w + 7) / 8, ty = (h + 7) / 8;
-  const RpSpan in = rp_span(d_light, light_stride, w, h, sizeof(rt4_light_px));
-  RpSpan outs[3];
-  int n_out = 0;
-  outs[n_out++] = rp_span(d_tiles, tx, tx, ty, sizeof(uint32_t));
-  outs[n_out++] = rp_span(d_count, 1, 1, 1, sizeof(uint32_t));
-  if (d_tile_state) outs[n_out++] = rp_span(d_tile_state, tx, tx, ty, sizeof(int32_t));
-  for (int a = 0; a < n_out; a++) {
-    if (rp_overlap(outs[a], in)) return rt4_set_err(err, errlen, "an output overlaps the light accumulator"), RT4_ERR_ARG;
-    for (int b = a + 1; b < n_out; b++)
-      if (rp_overlap(outs[a], outs[b])) return rt4_set_err(err, errlen, "two outputs overlap"), RT4_ERR_ARG;
-  }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const unsigned tiles = static_cast<unsigned>(tx) * static_cast<unsigned>(ty);
-  if (ctx->select_cap < tiles) {  // more tiles than any call before: wait for the launches in flight, grow once
-    HIP_TRY(hipStreamSynchronize(s));
-    if (ctx->launched) HIP_TRY(hipEventSynchronize(ctx->done));
-    if (ctx->d_select) (void)hipFree(ctx->d_select);
-    ctx->d_select = nullptr;
-    ctx->select_cap = 0;
-    HIP_TRY(hipMalloc(&ctx->d_select, static_cast<size_t>(tiles) * sizeof(uint32_t)));
-    ctx->select_cap = tiles;
-  }
-  int rc = order_launch(ctx, s, err, errlen);
-  if (rc != RT4_OK) return rc;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(rt4_light_tile_flags_kernel, dim3(std::min((tiles + 3u) / 4u, SELECT_MAX_BLOCKS)), dim3(256), 0, s,
-                     d_light, light_stride, w, h, k, params->threshold, params->min_above, params->min_frames, ctx->d_select);
-  hipError_t le = hipGetLastError();
-  if (le == hipSuccess) {
-    hipLaunchKernelGGL(rt4_light_tile_compact_kernel, dim3(1), dim3(SELECT_CHUNK), 0, s, ctx->d_select, tx, ty,
-                       params->dilate, d_tiles, d_count, d_tile_state);
-    le = hipGetLastError();
-  }
-  rc = done_launch(ctx, s, err, errlen);
-  if (le != hipSuccess) {
-    rt4_set_err(err, errlen, "tile selection launch failed: %s", hipGetErrorString(le));
-    return RT4_ERR_HIP;
-  }
-  return rc;
+  st = grow_scratch(ctx, ctx->select, s, tiles, sizeof(uint32_t), err, errlen);  // more tiles than any call before
+  if (st != RT4_OK) return st;
+  uint32_t* flags = static_cast<uint32_t*>(ctx->select.d);
+  return post_launch(ctx, s, "tile selection", err, errlen, [&] {
+    hipLaunchKernelGGL(rt4_light_tile_flags_kernel, dim3(std::min((tiles + 3u) / 4u, SELECT_MAX_BLOCKS)), dim3(256), 0, s,
+                       d_light, light_stride, w, h, k, params->threshold, params->min_above, params->min_frames, flags);
+    hipError_t le = hipGetLastError();
+    if (le == hipSuccess) {
+      hipLaunchKernelGGL(rt4_light_tile_compact_kernel, dim3(1), dim3(SELECT_CHUNK), 0, s, flags, tx, ty, params->dilate,
+                         d_tiles, d_count, d_tile_state);
+      le = hipGetLastError();
+    }
+    return le;
+  });
 }
 
 int rt4_light_select_tiles_host(rt4_context* ctx, const rt4_light_px* light, int64_t light_stride, int32_t w, int32_t h,
@@ -267,16 +246,15 @@ int rt4_light_select_tiles_host(rt4_context* ctx, const rt4_light_px* light, int
   if (!ctx || !light || !params || !tiles || !count) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
   if (w <= 0 || h <= 0 || light_stride < w) return rt4_set_err(err, errlen, "bad image size or row stride"), RT4_ERR_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
-  LightStage acc, dl, dc, ds;
+  HostStage acc, dl, dc, ds;
   const size_t n_tiles = static_cast<size_t>((w + 7) / 8) * static_cast<size_t>((h + 7) / 8);
   hipError_t e = acc.up(light, image_span(light_stride, w, h) * sizeof(rt4_light_px));
   if (e == hipSuccess) e = dl.up(tiles, n_tiles * sizeof(uint32_t));
   if (e == hipSuccess) e = dc.up(count, sizeof(uint32_t));
   if (e == hipSuccess && tile_state) e = ds.up(tile_state, n_tiles * sizeof(int32_t));
   if (e == hipSuccess) {
-    const int st = rt4_light_select_tiles_device(ctx, static_cast<const rt4_light_px*>(acc.d), light_stride, w, h, k, params,
-                                                 static_cast<uint32_t*>(dl.d), static_cast<uint32_t*>(dc.d),
-                                                 static_cast<int32_t*>(ds.d), nullptr, err, errlen);
+    const int st = rt4_light_select_tiles_device(ctx, acc.as<const rt4_light_px>(), light_stride, w, h, k, params,
+                                                 dl.as<uint32_t>(), dc.as<uint32_t>(), ds.as<int32_t>(), nullptr, err, errlen);
     if (st != RT4_OK) return st;
     e = hipDeviceSynchronize();
     if (e == hipSuccess) e = dl.down(tiles);
@@ -290,51 +268,8 @@ int rt4_light_select_tiles_host(rt4_context* ctx, const rt4_light_px* light, int
 int rt4_render_light_tiles_device(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, const rt4_region* region,
                                   const uint32_t* d_tiles, int32_t n_tiles, rt4_light_px* d_light, int64_t row_stride_px,
                                   unsigned long long* d_counter, void* stream, char* err, size_t errlen) {
-  if (!ctx || !u || !region || !d_light) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
-  if (n_frames < 1) return rt4_set_err(err, errlen, "n_frames %d < 1", n_frames), RT4_ERR_ARG;
-  if (region->w > 8191 || region->h > 8191)
-    return rt4_set_err(err, errlen, "light accumulation: region %d x %d larger than 8191 x 8191", region->w, region->h),
-           RT4_ERR_ARG;
-  if (reinterpret_cast<uintptr_t>(d_light) % 16u != 0)
-    return rt4_set_err(err, errlen, "light accumulator not 16-byte aligned"), RT4_ERR_ARG;
-  for (int32_t f = 1; f < n_frames; f++) {  // only seed and part may change from frame to frame
-    rt4_uniforms x = u[f];
-    x.seed = u[0].seed;
-    x.part = u[0].part;
-    if (std::memcmp(&x, &u[0], sizeof x) != 0)
-      return rt4_set_err(err, errlen, "frame %d: uniforms other than seed/part differ from frame 0", f), RT4_ERR_ARG;
-  }
-  int st = rt4_check_render_args(u, region, row_stride_px, err, errlen);
-  if (st != RT4_OK) return st;
-  if (!ctx->has_scene) return rt4_set_err(err, errlen, "context has no scene (rt4_context_set_scene)"), RT4_ERR_ARG;
-  const int64_t tiles = static_cast<int64_t>((region->w + 7) / 8) * ((region->h + 7) / 8);
-  if (n_tiles < 0 || n_tiles > tiles)
-    return rt4_set_err(err, errlen, "n_tiles %d not in [0, %lld]", n_tiles, static_cast<long long>(tiles)), RT4_ERR_ARG;
-  if (n_tiles > 0 && (!d_tiles || reinterpret_cast<uintptr_t>(d_tiles) % 4u != 0))
-    return rt4_set_err(err, errlen, "tile list NULL or not 4-byte aligned"), RT4_ERR_ARG;
-  if (n_tiles == 0) return RT4_OK;
-  rt4_section_job job;
-  job.region = *region;
-  job.d_frame = d_light;
-  job.row_stride_px = row_stride_px;
-  const LightTarget lt{d_light, row_stride_px};
   const TileList tl{d_tiles, n_tiles};
-  const int32_t chunk = rt4_context_frames_per_launch(ctx, region->w, region->h);
-  int32_t seeds[RT4_MAX_FRAMES];
-  float parts[RT4_MAX_FRAMES];
-  for (int32_t f0 = 0; f0 < n_frames; f0 += chunk) {
-    const int32_t n = std::min(chunk, n_frames - f0);
-    job.u = u[f0];
-    job.u.part = 1.0f;
-    for (int32_t f = 0; f < n; f++) {
-      seeds[f] = u[f0 + f].seed;
-      parts[f] = 1.0f;
-    }
-    const FramePlan fp{n, seeds, parts};
-    st = launch_jobs(ctx, &job, 1, RT4_FRAME_RGBA32F, d_counter, stream, err, errlen, &fp, &lt, &tl);
-    if (st != RT4_OK) return st;
-  }
-  return RT4_OK;
+  return render_light(ctx, u, n_frames, region, &tl, d_light, row_stride_px, d_counter, stream, err, errlen);
 }
 
 int rt4_render_light_tiles_host(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, const rt4_region* region,
@@ -347,25 +282,8 @@ int rt4_render_light_tiles_host(rt4_context* ctx, const rt4_uniforms* u, int32_t
   if (n_tiles < 0 || (n_tiles > 0 && !tiles)) return rt4_set_err(err, errlen, "bad tile list"), RT4_ERR_ARG;
   if (n_intersections) *n_intersections = 0;
   if (region->w == 0 || region->h == 0) return n_tiles == 0 ? RT4_OK : (rt4_set_err(err, errlen, "n_tiles %d not 0", n_tiles), RT4_ERR_ARG);
-  HIP_TRY(hipSetDevice(ctx->device));
-  LightStage acc, cnt, lst;
-  hipError_t e = acc.up(light, image_span(row_stride_px, region->w, region->h) * sizeof(rt4_light_px));
-  if (e == hipSuccess) e = cnt.up(nullptr, sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemset(cnt.d, 0, sizeof(unsigned long long));
-  if (e == hipSuccess && n_tiles > 0) e = lst.up(tiles, static_cast<size_t>(n_tiles) * sizeof(uint32_t));
-  if (e == hipSuccess) {
-    st = rt4_render_light_tiles_device(ctx, u, n_frames, region, static_cast<const uint32_t*>(lst.d), n_tiles,
-                                       static_cast<rt4_light_px*>(acc.d), row_stride_px,
-                                       static_cast<unsigned long long*>(cnt.d), nullptr, err, errlen);
-    if (st != RT4_OK) return st;
-    e = hipDeviceSynchronize();
-    unsigned long long c = 0;
-    if (e == hipSuccess) e = acc.down(light);
-    if (e == hipSuccess) e = hipMemcpy(&c, cnt.d, sizeof c, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && n_intersections) *n_intersections = c;
-  }
-  if (e != hipSuccess) return rt4_set_err(err, errlen, "render_light_tiles_host failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
-  return RT4_OK;
+  return render_light_staged(ctx, u, n_frames, region, true, tiles, n_tiles, light, row_stride_px, n_intersections,
+                             "render_light_tiles_host", err, errlen);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // rt4_temporal.h — temporal reprojection of rt4.h (rt4_reproject_device, rt4_temporal_blend_device, rt4_temporal;
-// DESIGN.md §4.34): kernels and entry points. Part of rt4_trace.hip's translation unit (included at its end, after
-// rt4_denoise.h: the context, the blend_* store helpers, the launch ordering and image_span live there); no trace
-// kernel uses anything from here.
+// DESIGN.md §4.34): kernels and entry points. From rt4_post.h: the argument checks, the launch bracket, the pixel
+// grid, px_decode / px_store_opaque, HostStage and alloc_zeroed; from no other pass. rt4_upscale.h takes RpCam, rp_cam,
+// rp_primary and rp_same_pose from here. No trace kernel uses anything from here.
 //
 // Reprojection is a gather: one lane per pixel of the new view in 32x8 blocks. The lane rebuilds its hit point from
 // the new G-buffer, projects it into the old camera (both cameras are kernel arguments: SGPRs), and reads up to four
@@ -11,8 +11,6 @@
 #pragma once
 
 namespace {
-
-constexpr int RP_BX = 32, RP_BY = 8;  // pixels per workgroup (one lane each)
 
 struct RpCam {  // what a primary ray and a projection need of rt4_uniforms
   float res[2], mtr[2], focus[4], vec[4], top[4], right[4];
@@ -52,24 +50,10 @@ __device__ __forceinline__ V4 rp_primary(const RpCam& c, int x, int y) {
   return divs(dd, length(dd));
 }
 
-__device__ __forceinline__ V3 rp_decode(const void* frame, int64_t at, int32_t format) {
-  if (format == RT4_FRAME_RGBA16F) {
-    const h4v v = reinterpret_cast<const h4v*>(frame)[at];
-    return V3{static_cast<float>(v[0]), static_cast<float>(v[1]), static_cast<float>(v[2])};
-  }
-  if (format == RT4_FRAME_RGBA8) {
-    const uint32_t v = reinterpret_cast<const uint32_t*>(frame)[at];
-    return V3{static_cast<float>(v & 0xFFu) / 255.0f, static_cast<float>((v >> 8) & 0xFFu) / 255.0f,
-              static_cast<float>((v >> 16) & 0xFFu) / 255.0f};
-  }
-  const float4 v = reinterpret_cast<const float4*>(frame)[at];
-  return V3{v.x, v.y, v.z};
-}
-
 // rt4.h rt4_reproject_device, steps 1-6.
 __global__ __launch_bounds__(256) void rt4_reproject_kernel(const RpArgs a) {
-  const int x = static_cast<int>(blockIdx.x) * RP_BX + static_cast<int>(threadIdx.x & 31u);
-  const int y = static_cast<int>(blockIdx.y) * RP_BY + static_cast<int>(threadIdx.x >> 5);
+  const int2 xy = px_xy();
+  const int x = xy.x, y = xy.y;
   const int w = a.w, h = a.h;
   if (x >= w || y >= h) return;
   const float4* gp = reinterpret_cast<const float4*>(a.gcur + static_cast<int64_t>(y) * a.gcur_stride + x);
@@ -115,7 +99,7 @@ __global__ __launch_bounds__(256) void rt4_reproject_kernel(const RpArgs a) {
               if (!(dot(np, V4{nq.x, nq.y, nq.z, nq.w}) >= a.cos_min)) continue;
               const V4 Xq = mad(rp_primary(a.prev, qx, qy), mq.x, fp);
               if (!(__builtin_fabsf(dot(np, sub(Xq, X))) <= tol)) continue;  // off the new hit's tangent plane
-              const V3 c = rp_decode(a.accp, static_cast<int64_t>(qy) * a.accp_stride + qx, a.format);
+              const float4 c = px_decode(a.accp, a.format, static_cast<int64_t>(qy) * a.accp_stride + qx);
               ar = __fadd_rn(ar, __fmul_rn(k, c.x));
               ag = __fadd_rn(ag, __fmul_rn(k, c.y));
               ab = __fadd_rn(ab, __fmul_rn(k, c.z));
@@ -127,7 +111,8 @@ __global__ __launch_bounds__(256) void rt4_reproject_kernel(const RpArgs a) {
       }
     }
   }
-  // 6. blend_*(c, 1, 0) is the store rule of the format (rt4_denoise.h); a restarted pixel stores the zero colour
+  // 6. a restarted pixel stores the zero colour. px_store_opaque written out: calling it here changes this kernel's
+  // generated code (one more instruction), and a refactoring may not.
   const bool kept = wsum > 0.0f;
   const V3 c = kept ? V3{ar / wsum, ag / wsum, ab / wsum} : V3{0.0f, 0.0f, 0.0f};
   const int64_t ao = static_cast<int64_t>(y) * a.acco_stride + x;
@@ -148,8 +133,8 @@ __global__ __launch_bounds__(256) void rt4_temporal_blend_kernel(const float4* _
                                                                  void* __restrict__ acc, int64_t acc_stride, int32_t format,
                                                                  int32_t* __restrict__ hist, int64_t hist_stride, int32_t w,
                                                                  int32_t h) {
-  const int x = static_cast<int>(blockIdx.x) * RP_BX + static_cast<int>(threadIdx.x & 31u);
-  const int y = static_cast<int>(blockIdx.y) * RP_BY + static_cast<int>(threadIdx.x >> 5);
+  const int2 xy = px_xy();
+  const int x = xy.x, y = xy.y;
   if (x >= w || y >= h) return;
   int32_t* hp = hist + static_cast<int64_t>(y) * hist_stride + x;
   const int32_t n0 = *hp, n = n0 == INT32_MAX ? n0 : n0 + 1;
@@ -169,15 +154,6 @@ __global__ __launch_bounds__(256) void rt4_temporal_blend_kernel(const float4* _
   }
   *hp = n;
 }
-
-struct RpSpan {  // the bytes [b, e) of one strided image
-  uintptr_t b, e;
-};
-RpSpan rp_span(const void* p, int64_t stride_px, int32_t w, int32_t h, size_t elem) {
-  const uintptr_t b = reinterpret_cast<uintptr_t>(p);
-  return RpSpan{b, b + image_span(stride_px, w, h) * elem};
-}
-bool rp_overlap(RpSpan a, RpSpan b) { return a.b < b.e && b.b < a.e; }
 
 // The pose of a frame: the bytes of resolution, mtr_sizes, focus, vec_to_mtr, top_drct, right_drct.
 bool rp_same_pose(const rt4_uniforms* a, const rt4_uniforms* b) {
@@ -221,29 +197,22 @@ int rt4_reproject_device(rt4_context* ctx, const rt4_uniforms* u_cur, const rt4_
                          int32_t w, int32_t h, const rt4_reproject_params* params, void* stream, char* err, size_t errlen) {
   if (!ctx || !u_cur || !d_gcur || !u_prev || !d_gprev || !d_acc_prev || !d_hist_prev || !d_acc_out || !d_hist_out || !params)
     return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
-  const int32_t px_bytes = rt4_frame_format_bytes(format);
+  const size_t px_bytes = static_cast<size_t>(rt4_frame_format_bytes(format));
   if (px_bytes == 0) return rt4_set_err(err, errlen, "unknown frame format %d", format), RT4_ERR_ARG;
   if (w <= 0 || h <= 0 || w > 65535 || h > 65535)
     return rt4_set_err(err, errlen, "frame size %d x %d not in [1, 65535]", w, h), RT4_ERR_ARG;
   const float fw = static_cast<float>(w), fh = static_cast<float>(h);
   if (u_cur->resolution[0] != fw || u_cur->resolution[1] != fh || u_prev->resolution[0] != fw || u_prev->resolution[1] != fh)
     return rt4_set_err(err, errlen, "the uniforms' resolution is not the frame size %d x %d", w, h), RT4_ERR_ARG;
-  if (gcur_stride < w || gprev_stride < w || accp_stride < w || histp_stride < w || acco_stride < w || histo_stride < w)
-    return rt4_set_err(err, errlen, "row stride smaller than width"), RT4_ERR_ARG;
   if (params->max_history < 1) return rt4_set_err(err, errlen, "max_history %d below 1", params->max_history), RT4_ERR_ARG;
-  const RpSpan in[4] = {rp_span(d_gcur, gcur_stride, w, h, sizeof(rt4_gbuffer_px)),
-                        rp_span(d_gprev, gprev_stride, w, h, sizeof(rt4_gbuffer_px)),
-                        rp_span(d_acc_prev, accp_stride, w, h, static_cast<size_t>(px_bytes)),
-                        rp_span(d_hist_prev, histp_stride, w, h, sizeof(int32_t))};
-  const RpSpan out[2] = {rp_span(d_acc_out, acco_stride, w, h, static_cast<size_t>(px_bytes)),
-                         rp_span(d_hist_out, histo_stride, w, h, sizeof(int32_t))};
-  if (in[0].b % 16u != 0 || in[1].b % 16u != 0 || in[2].b % px_bytes != 0 || out[0].b % px_bytes != 0 || in[3].b % 4u != 0 ||
-      out[1].b % 4u != 0)
-    return rt4_set_err(err, errlen, "G-buffer, frame or history not aligned to its pixel size"), RT4_ERR_ARG;
-  if (rp_overlap(out[0], out[1])) return rt4_set_err(err, errlen, "the two outputs overlap"), RT4_ERR_ARG;
-  for (const RpSpan& o : out)
-    for (const RpSpan& i : in)
-      if (rp_overlap(o, i)) return rt4_set_err(err, errlen, "an output overlaps an input"), RT4_ERR_ARG;
+  const PostImage in[4] = {post_image(d_gcur, gcur_stride, w, h, sizeof(rt4_gbuffer_px), "current G-buffer"),
+                           post_image(d_gprev, gprev_stride, w, h, sizeof(rt4_gbuffer_px), "previous G-buffer"),
+                           post_image(d_acc_prev, accp_stride, w, h, px_bytes, "previous accumulator"),
+                           post_image(d_hist_prev, histp_stride, w, h, sizeof(int32_t), "previous history")};
+  const PostImage out[2] = {post_image(d_acc_out, acco_stride, w, h, px_bytes, "output accumulator"),
+                            post_image(d_hist_out, histo_stride, w, h, sizeof(int32_t), "output history")};
+  const int st = post_check_args(out, 2, in, 4, err, errlen);
+  if (st != RT4_OK) return st;
   RpArgs a;
   a.cur = rp_cam(u_cur);
   a.prev = rp_cam(u_prev);
@@ -268,18 +237,10 @@ int rt4_reproject_device(rt4_context* ctx, const rt4_uniforms* u_cur, const rt4_
   a.slice_tol = params->slice_tol;
   a.max_refl_prob = params->max_refl_prob;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int rc = order_launch(ctx, s, err, errlen);
-  if (rc != RT4_OK) return rc;
-  const dim3 grid(static_cast<unsigned>((w + RP_BX - 1) / RP_BX), static_cast<unsigned>((h + RP_BY - 1) / RP_BY)), block(256);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(rt4_reproject_kernel, grid, block, 0, s, a);
-  const hipError_t le = hipGetLastError();
-  rc = done_launch(ctx, s, err, errlen);
-  if (le != hipSuccess) {
-    rt4_set_err(err, errlen, "reproject kernel launch failed: %s", hipGetErrorString(le));
-    return RT4_ERR_HIP;
-  }
-  return rc;
+  return post_launch(ctx, s, "reproject kernel", err, errlen, [&] {
+    hipLaunchKernelGGL(rt4_reproject_kernel, px_grid(w, h), dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 int rt4_reproject_host(rt4_context* ctx, const rt4_uniforms* u_cur, const rt4_gbuffer_px* gcur, int64_t gcur_stride,
@@ -295,71 +256,46 @@ int rt4_reproject_host(rt4_context* ctx, const rt4_uniforms* u_cur, const rt4_gb
       histo_stride < w)
     return rt4_set_err(err, errlen, "bad frame size or row stride"), RT4_ERR_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
-  // the six images in order: gcur, gprev, acc_prev, hist_prev (inputs), acc_out, hist_out (outputs)
-  const void* host[6] = {gcur, gprev, acc_prev, hist_prev, acc_out, hist_out};
-  const size_t bytes[6] = {image_span(gcur_stride, w, h) * sizeof(rt4_gbuffer_px),
-                           image_span(gprev_stride, w, h) * sizeof(rt4_gbuffer_px),
-                           image_span(accp_stride, w, h) * static_cast<size_t>(px_bytes),
-                           image_span(histp_stride, w, h) * sizeof(int32_t),
-                           image_span(acco_stride, w, h) * static_cast<size_t>(px_bytes),
-                           image_span(histo_stride, w, h) * sizeof(int32_t)};
-  void* d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  for (int q = 0; q < 6 && e == hipSuccess; q++) {
-    e = hipMalloc(&d[q], bytes[q]);
-    if (e == hipSuccess) e = hipMemcpy(d[q], host[q], bytes[q], hipMemcpyHostToDevice);  // outputs: the padding keeps its bytes
-  }
-  int st = RT4_OK;
+  HostStage gc, gp, ap, hp, ao, ho;
+  hipError_t e = gc.up(gcur, image_span(gcur_stride, w, h) * sizeof(rt4_gbuffer_px));
+  if (e == hipSuccess) e = gp.up(gprev, image_span(gprev_stride, w, h) * sizeof(rt4_gbuffer_px));
+  if (e == hipSuccess) e = ap.up(acc_prev, image_span(accp_stride, w, h) * static_cast<size_t>(px_bytes));
+  if (e == hipSuccess) e = hp.up(hist_prev, image_span(histp_stride, w, h) * sizeof(int32_t));
+  if (e == hipSuccess) e = ao.up(acc_out, image_span(acco_stride, w, h) * static_cast<size_t>(px_bytes));
+  if (e == hipSuccess) e = ho.up(hist_out, image_span(histo_stride, w, h) * sizeof(int32_t));
   if (e == hipSuccess) {
-    st = rt4_reproject_device(ctx, u_cur, static_cast<const rt4_gbuffer_px*>(d[0]), gcur_stride, u_prev,
-                              static_cast<const rt4_gbuffer_px*>(d[1]), gprev_stride, d[2], accp_stride,
-                              static_cast<const int32_t*>(d[3]), histp_stride, d[4], acco_stride, static_cast<int32_t*>(d[5]),
-                              histo_stride, format, w, h, params, nullptr, err, errlen);
-    if (st == RT4_OK) {
-      e = hipDeviceSynchronize();
-      if (e == hipSuccess) e = hipMemcpy(acc_out, d[4], bytes[4], hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(hist_out, d[5], bytes[5], hipMemcpyDeviceToHost);
-    }
+    const int st = rt4_reproject_device(ctx, u_cur, gc.as<const rt4_gbuffer_px>(), gcur_stride, u_prev,
+                                        gp.as<const rt4_gbuffer_px>(), gprev_stride, ap.d, accp_stride, hp.as<const int32_t>(),
+                                        histp_stride, ao.d, acco_stride, ho.as<int32_t>(), histo_stride, format, w, h, params,
+                                        nullptr, err, errlen);
+    if (st != RT4_OK) return st;
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = ao.down(acc_out);
+    if (e == hipSuccess) e = ho.down(hist_out);
   }
-  for (void* p : d)
-    if (p) (void)hipFree(p);
-  if (st == RT4_OK && e != hipSuccess) {
-    rt4_set_err(err, errlen, "reproject_host failed: %s", hipGetErrorString(e));
-    st = RT4_ERR_HIP;
-  }
-  return st;
+  if (e != hipSuccess) return rt4_set_err(err, errlen, "reproject_host failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
+  return RT4_OK;
 }
 
 int rt4_temporal_blend_device(rt4_context* ctx, const float* d_new_rgba32f, int64_t new_stride, void* d_acc, int64_t acc_stride,
                               int32_t format, int32_t* d_hist, int64_t hist_stride, int32_t w, int32_t h, void* stream,
                               char* err, size_t errlen) {
   if (!ctx || !d_new_rgba32f || !d_acc || !d_hist) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
-  const int32_t px_bytes = rt4_frame_format_bytes(format);
+  const size_t px_bytes = static_cast<size_t>(rt4_frame_format_bytes(format));
   if (px_bytes == 0) return rt4_set_err(err, errlen, "unknown frame format %d", format), RT4_ERR_ARG;
   if (w <= 0 || h <= 0 || w > 65535 || h > 65535)
     return rt4_set_err(err, errlen, "frame size %d x %d not in [1, 65535]", w, h), RT4_ERR_ARG;
-  if (new_stride < w || acc_stride < w || hist_stride < w)
-    return rt4_set_err(err, errlen, "row stride smaller than width"), RT4_ERR_ARG;
-  const RpSpan sn = rp_span(d_new_rgba32f, new_stride, w, h, 16u), sa = rp_span(d_acc, acc_stride, w, h, static_cast<size_t>(px_bytes)),
-               sh = rp_span(d_hist, hist_stride, w, h, sizeof(int32_t));
-  if (sn.b % 16u != 0 || sa.b % px_bytes != 0 || sh.b % 4u != 0)
-    return rt4_set_err(err, errlen, "frame or history not aligned to its pixel size"), RT4_ERR_ARG;
-  if (rp_overlap(sn, sa) || rp_overlap(sn, sh) || rp_overlap(sa, sh))
-    return rt4_set_err(err, errlen, "the sample frame, the accumulator and the history overlap"), RT4_ERR_ARG;
+  const PostImage in = post_image(d_new_rgba32f, new_stride, w, h, 16u, "sample frame");
+  const PostImage out[2] = {post_image(d_acc, acc_stride, w, h, px_bytes, "accumulator"),  // both read and written
+                            post_image(d_hist, hist_stride, w, h, sizeof(int32_t), "history")};
+  const int st = post_check_args(out, 2, &in, 1, err, errlen);
+  if (st != RT4_OK) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int rc = order_launch(ctx, s, err, errlen);
-  if (rc != RT4_OK) return rc;
-  const dim3 grid(static_cast<unsigned>((w + RP_BX - 1) / RP_BX), static_cast<unsigned>((h + RP_BY - 1) / RP_BY)), block(256);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(rt4_temporal_blend_kernel, grid, block, 0, s, reinterpret_cast<const float4*>(d_new_rgba32f), new_stride,
-                     d_acc, acc_stride, format, d_hist, hist_stride, w, h);
-  const hipError_t le = hipGetLastError();
-  rc = done_launch(ctx, s, err, errlen);
-  if (le != hipSuccess) {
-    rt4_set_err(err, errlen, "temporal blend kernel launch failed: %s", hipGetErrorString(le));
-    return RT4_ERR_HIP;
-  }
-  return rc;
+  return post_launch(ctx, s, "temporal blend kernel", err, errlen, [&] {
+    hipLaunchKernelGGL(rt4_temporal_blend_kernel, px_grid(w, h), dim3(256), 0, s, reinterpret_cast<const float4*>(d_new_rgba32f),
+                       new_stride, d_acc, acc_stride, format, d_hist, hist_stride, w, h);
+    return hipGetLastError();
+  });
 }
 
 // ---- rt4_temporal -------------------------------------------------------------------------------------------------
@@ -399,15 +335,12 @@ int rt4_temporal_create(rt4_context* ctx, int32_t w, int32_t h, int32_t format, 
   const size_t npx = static_cast<size_t>(w) * static_cast<size_t>(h);
   hipError_t e = hipSuccess;
   for (int q = 0; q < 2 && e == hipSuccess; q++) {
-    e = hipMalloc(&t->d_acc[q], npx * static_cast<size_t>(px_bytes));
-    if (e == hipSuccess) e = hipMemset(t->d_acc[q], 0, npx * static_cast<size_t>(px_bytes));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->d_hist[q]), npx * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemset(t->d_hist[q], 0, npx * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->d_gbuf[q]), npx * sizeof(rt4_gbuffer_px));
-    if (e == hipSuccess) e = hipMemset(t->d_gbuf[q], 0, npx * sizeof(rt4_gbuffer_px));
+    e = alloc_zeroed(&t->d_acc[q], npx * static_cast<size_t>(px_bytes));
+    if (e == hipSuccess) e = alloc_zeroed(reinterpret_cast<void**>(&t->d_hist[q]), npx * sizeof(int32_t));
+    if (e == hipSuccess) e = alloc_zeroed(reinterpret_cast<void**>(&t->d_gbuf[q]), npx * sizeof(rt4_gbuffer_px));
   }
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->d_sample), npx * 16u);
-  if (e == hipSuccess) e = hipMemset(t->d_sample, 0, npx * 16u);  // finite: a render with part = 1 then stores the colour itself
+  // finite: a render with part = 1 then stores the colour itself
+  if (e == hipSuccess) e = alloc_zeroed(reinterpret_cast<void**>(&t->d_sample), npx * 16u);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
     rt4_set_err(err, errlen, "temporal_create failed: %s", hipGetErrorString(e));
@@ -441,11 +374,9 @@ int rt4_temporal_frame_device(rt4_temporal* t, const rt4_uniforms* u, const rt4_
   if (t->first) {  // (a) the history restarts: hist = 0 makes the blend below store the sample
     st = rt4_render_gbuffer_device(ctx, u, &reg, t->d_gbuf[t->cur], stride, stream, err, errlen);
     if (st != RT4_OK) return st;
-    st = order_launch(ctx, s, err, errlen);  // the memset is a launch of the context's like any other
-    if (st != RT4_OK) return st;
-    const hipError_t e = hipMemsetAsync(t->d_hist[t->cur], 0, static_cast<size_t>(t->w) * static_cast<size_t>(t->h) * sizeof(int32_t), s);
-    st = done_launch(ctx, s, err, errlen);
-    if (e != hipSuccess) return rt4_set_err(err, errlen, "temporal_frame: %s", hipGetErrorString(e)), RT4_ERR_HIP;
+    st = post_launch(ctx, s, "temporal_frame: history reset", err, errlen, [&] {  // a launch of the context's like any other
+      return hipMemsetAsync(t->d_hist[t->cur], 0, static_cast<size_t>(t->w) * static_cast<size_t>(t->h) * sizeof(int32_t), s);
+    });
     if (st != RT4_OK) return st;
   } else if (!rp_same_pose(u, &t->prev)) {  // (b) the camera moved: carry image and history over
     const int nxt = 1 - t->cur;

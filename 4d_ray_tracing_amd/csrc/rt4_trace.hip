@@ -1687,6 +1687,11 @@ const Variant& variant_for(uint32_t shape) {
 }  // namespace
 
 // ==================================================================================== context
+struct CtxScratch {  // a device buffer of the context that grows to the largest need (grow_scratch, rt4_post.h)
+  void* d = nullptr;
+  size_t cap = 0;  // units it holds
+};
+
 struct rt4_context {
   int device = 0;
   uint32_t flags = 0;
@@ -1728,19 +1733,15 @@ struct rt4_context {
   unsigned long long* d_ocount = nullptr;  // one counter per slot
   // Scratch of rt4_denoise_device (rt4_denoise.h): two fp32 RGBA images for the levels and the repacked guide
   // (normal 16 B, {id, depth} 8 B), 56 B per pixel of the largest frame filtered, in one allocation.
-  void* d_denoise = nullptr;
-  size_t denoise_px = 0;  // pixels it holds
+  CtxScratch denoise;  // in pixels
   // Scratch of rt4_light_denoise_device (rt4_light_denoise.h), separate from the colour filter's: two states
   // ({L, Y} 16 B, V 4 B) and the repacked guide (24 B), 64 B per pixel of the largest image filtered, in one allocation.
-  void* d_light_denoise = nullptr;
-  size_t light_denoise_px = 0;  // pixels it holds
+  CtxScratch light_denoise;  // in pixels
   // Scratch of adaptive light sampling (rt4_light_tiles.h): the per-tile flags of rt4_light_select_tiles_device, and the
   // clamped copy of a tile list that rt4_render_light_tiles_device hands the trace kernel (followed by the two words
   // {0, 1} it reads as KernelArgs::order_ends). Apart from d_order: the pre-pass order stays valid across tile launches.
-  uint32_t* d_select = nullptr;
-  size_t select_cap = 0;  // tiles it holds
-  uint32_t* d_tile_list = nullptr;
-  size_t tile_list_cap = 0;  // tiles it holds (+ 2 words)
+  CtxScratch select;     // in 4-B words: one per tile
+  CtxScratch tile_list;  // in 4-B words: one per tile and the two at the end
 };
 
 #define HIP_TRY(expr)                                                                            \
@@ -2204,10 +2205,8 @@ void rt4_context_destroy(rt4_context* ctx) {
   if (ctx->d_ocount) (void)hipFree(ctx->d_ocount);
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
   if (ctx->d_eval) (void)hipFree(ctx->d_eval);
-  if (ctx->d_denoise) (void)hipFree(ctx->d_denoise);
-  if (ctx->d_light_denoise) (void)hipFree(ctx->d_light_denoise);
-  if (ctx->d_select) (void)hipFree(ctx->d_select);
-  if (ctx->d_tile_list) (void)hipFree(ctx->d_tile_list);
+  for (const CtxScratch* sc : {&ctx->denoise, &ctx->light_denoise, &ctx->select, &ctx->tile_list})
+    if (sc->d) (void)hipFree(sc->d);
   delete ctx;
 }
 
@@ -2947,32 +2946,14 @@ int rt4_debug_final_light(rt4_context* ctx, const float* drct, float* out, int64
 }  // extern "C"
 
 // ==================================================================================== G-buffer, denoiser
-namespace {
-
-// A launch of the context on stream s that is not a render (G-buffer, denoise): ordered behind the context's previous
-// launch when that ran on another stream. done_launch() afterwards: rt4_context_set_scene and the next launch on
-// another stream wait for it.
-int order_launch(rt4_context* ctx, hipStream_t s, char* err, size_t errlen) {
-  if (ctx->launched && s != ctx->last_stream) HIP_TRY(hipStreamWaitEvent(s, ctx->done, 0));
-  return RT4_OK;
-}
-int done_launch(rt4_context* ctx, hipStream_t s, char* err, size_t errlen) {
-  const hipError_t re = hipEventRecord(ctx->done, s);
-  ctx->last_stream = s;
-  ctx->launched = true;
-  if (re != hipSuccess) {
-    rt4_set_err(err, errlen, "hipEventRecord failed: %s", hipGetErrorString(re));
-    return RT4_ERR_HIP;
-  }
-  return RT4_OK;
-}
-
-// Elements of a strided w x h image: the last row ends at its w-th pixel.
-size_t image_span(int64_t stride_px, int32_t w, int32_t h) {
-  return static_cast<size_t>(h - 1) * static_cast<size_t>(stride_px) + static_cast<size_t>(w);
-}
-
-}  // namespace
+// The layer the G-buffer entry points below and every post pass share, then the passes.
+#include "rt4_post.h"
+#include "rt4_denoise.h"
+#include "rt4_temporal.h"
+#include "rt4_upscale.h"
+#include "rt4_light.h"
+#include "rt4_light_denoise.h"
+#include "rt4_light_tiles.h"
 
 extern "C" {
 
@@ -3002,18 +2983,11 @@ int rt4_render_gbuffer_device(rt4_context* ctx, const rt4_uniforms* u, const rt4
   J.tiles_x = static_cast<unsigned>((region->w + 7) / 8);
   g.tiles = J.tiles_x * static_cast<unsigned>((region->h + 7) / 8);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int rc = order_launch(ctx, s, err, errlen);
-  if (rc != RT4_OK) return rc;
-  (void)hipGetLastError();  // a sticky error of an earlier, unrelated call must not be taken for this launch's
-  hipLaunchKernelGGL(variant_for(ctx->shape).gbuffer, dim3((g.tiles + 3u) / 4u), dim3(256), 0, s, ctx->d_scene,
-                     scene_aux(ctx), g, d_gbuf);
-  const hipError_t le = hipGetLastError();
-  rc = done_launch(ctx, s, err, errlen);
-  if (le != hipSuccess) {
-    rt4_set_err(err, errlen, "G-buffer kernel launch failed: %s", hipGetErrorString(le));
-    return RT4_ERR_HIP;
-  }
-  return rc;
+  return post_launch(ctx, s, "G-buffer kernel", err, errlen, [&] {
+    hipLaunchKernelGGL(variant_for(ctx->shape).gbuffer, dim3((g.tiles + 3u) / 4u), dim3(256), 0, s, ctx->d_scene,
+                       scene_aux(ctx), g, d_gbuf);
+    return hipGetLastError();
+  });
 }
 
 int rt4_render_gbuffer_host(rt4_context* ctx, const rt4_uniforms* u, const rt4_region* region, rt4_gbuffer_px* gbuf,
@@ -3023,31 +2997,16 @@ int rt4_render_gbuffer_host(rt4_context* ctx, const rt4_uniforms* u, const rt4_r
     return rt4_set_err(err, errlen, "bad region or row stride"), RT4_ERR_ARG;
   if (region->w == 0 || region->h == 0) return RT4_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  const size_t bytes = image_span(row_stride_px, region->w, region->h) * sizeof(rt4_gbuffer_px);
-  void* d = nullptr;
-  HIP_TRY(hipMalloc(&d, bytes));
-  hipError_t e = hipMemcpy(d, gbuf, bytes, hipMemcpyHostToDevice);  // the padding between rows keeps its bytes
-  int st = RT4_OK;
+  HostStage g;
+  hipError_t e = g.up(gbuf, image_span(row_stride_px, region->w, region->h) * sizeof(rt4_gbuffer_px));
   if (e == hipSuccess) {
-    st = rt4_render_gbuffer_device(ctx, u, region, static_cast<rt4_gbuffer_px*>(d), row_stride_px, nullptr, err, errlen);
-    if (st == RT4_OK) {
-      e = hipDeviceSynchronize();
-      if (e == hipSuccess) e = hipMemcpy(gbuf, d, bytes, hipMemcpyDeviceToHost);
-    }
+    const int st = rt4_render_gbuffer_device(ctx, u, region, g.as<rt4_gbuffer_px>(), row_stride_px, nullptr, err, errlen);
+    if (st != RT4_OK) return st;
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = g.down(gbuf);
   }
-  (void)hipFree(d);
-  if (st == RT4_OK && e != hipSuccess) {
-    rt4_set_err(err, errlen, "render_gbuffer_host failed: %s", hipGetErrorString(e));
-    st = RT4_ERR_HIP;
-  }
-  return st;
+  if (e != hipSuccess) return rt4_set_err(err, errlen, "render_gbuffer_host failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
+  return RT4_OK;
 }
 
 }  // extern "C"
-
-#include "rt4_denoise.h"
-#include "rt4_temporal.h"
-#include "rt4_upscale.h"
-#include "rt4_light.h"
-#include "rt4_light_denoise.h"
-#include "rt4_light_tiles.h"

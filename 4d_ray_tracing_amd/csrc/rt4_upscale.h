@@ -1,6 +1,6 @@
 // rt4_upscale.h — window-resolution output of rt4.h (rt4_upscale_device, rt4_window): kernels and
-// entry points. Part of rt4_trace.hip's translation unit (included at its end, after rt4_temporal.h: the context, the
-// blend_* store helpers, the launch ordering, image_span and the Rp* camera helpers live there); no trace kernel uses
+// entry points. From rt4_post.h: the argument checks, the launch bracket, the pixel grid, px_decode / px_store_opaque,
+// HostStage and alloc_zeroed; from rt4_temporal.h: RpCam, rp_cam, rp_primary and rp_same_pose. No trace kernel uses
 // anything from here.
 //
 // The guided upscale is a gather: one lane per window pixel in 32x8 blocks. scale^2 window pixels share each cell, so
@@ -14,8 +14,7 @@
 
 namespace {
 
-constexpr int UP_BX = 32, UP_BY = 8;                    // window pixels per workgroup (one lane each)
-constexpr int UP_CELLS_MAX = (UP_BX + 2) * (UP_BY + 2);  // cells a block can tap: scale 1
+constexpr int UP_CELLS_MAX = (PX_BX + 2) * (PX_BY + 2);  // cells a block can tap: scale 1
 
 struct UpArgs {
   RpCam cells, win;
@@ -39,8 +38,8 @@ __device__ __forceinline__ void up_copy_cell(const void* src, int64_t si, void* 
 __global__ __launch_bounds__(256) void rt4_upscale_nearest_kernel(const void* __restrict__ src, int64_t src_stride,
                                                                   void* __restrict__ out, int64_t out_stride, int32_t format,
                                                                   int32_t W, int32_t H, int32_t s) {
-  const int x = static_cast<int>(blockIdx.x) * UP_BX + static_cast<int>(threadIdx.x & 31u);
-  const int y = static_cast<int>(blockIdx.y) * UP_BY + static_cast<int>(threadIdx.x >> 5);
+  const int2 xy = px_xy();
+  const int x = xy.x, y = xy.y;
   if (x >= W || y >= H) return;
   up_copy_cell(src, static_cast<int64_t>(y / s) * src_stride + x / s, out, static_cast<int64_t>(y) * out_stride + x, format);
 }
@@ -53,10 +52,10 @@ __global__ __launch_bounds__(256) void rt4_upscale_guided_kernel(const UpArgs a)
   __shared__ int l_s[UP_CELLS_MAX];
   const int s = a.s, cw = a.cw, ch = a.ch;
   const int W = cw * s, H = ch * s;
-  const int ox = static_cast<int>(blockIdx.x) * UP_BX, oy = static_cast<int>(blockIdx.y) * UP_BY;
+  const int ox = static_cast<int>(blockIdx.x) * PX_BX, oy = static_cast<int>(blockIdx.y) * PX_BY;
   // the cells this block can tap (block-uniform): one before the first pixel's cell, one after the last pixel's
   const int bx = ox / s - 1, by = oy / s - 1;
-  const int ncx = (ox + UP_BX - 1) / s - bx + 2, ncy = (oy + UP_BY - 1) / s - by + 2;  // <= 34, <= 10
+  const int ncx = (ox + PX_BX - 1) / s - bx + 2, ncy = (oy + PX_BY - 1) / s - by + 2;  // <= 34, <= 10
   const V4 focus = ld4(a.cells.focus);
   for (int k = static_cast<int>(threadIdx.x); k < ncx * ncy; k += 256) {
     const int ly = k / ncx, lx = k - ly * ncx;
@@ -70,7 +69,8 @@ __global__ __launch_bounds__(256) void rt4_upscale_guided_kernel(const UpArgs a)
       nq = V4{n4.x, n4.y, n4.z, n4.w};
       sq = __float_as_int(m.y);
       Xq = mad(rp_primary(a.cells, qx, qy), m.x, focus);
-      c = rp_decode(a.src, static_cast<int64_t>(qy) * a.src_stride + qx, a.format);
+      const float4 cq = px_decode(a.src, a.format, static_cast<int64_t>(qy) * a.src_stride + qx);
+      c = V3{cq.x, cq.y, cq.z};
     }
     l_x0[k] = Xq.x; l_x1[k] = Xq.y; l_x2[k] = Xq.z; l_x3[k] = Xq.w;
     l_n0[k] = nq.x; l_n1[k] = nq.y; l_n2[k] = nq.z; l_n3[k] = nq.w;
@@ -115,22 +115,13 @@ __global__ __launch_bounds__(256) void rt4_upscale_guided_kernel(const UpArgs a)
       wsum = __fadd_rn(wsum, k);
     }
   }
-  // 5. blend_*(c, 1, 0) is the store rule of the format (rt4_denoise.h)
+  // 5.
   const int64_t ao = static_cast<int64_t>(y) * a.out_stride + x;
   if (!(wsum > 0.0f)) {
     up_copy_cell(a.src, static_cast<int64_t>(cy) * a.src_stride + cx, a.out, ao, a.format);
     return;
   }
-  const V3 c{ar / wsum, ag / wsum, ab / wsum};
-  if (a.format == RT4_FRAME_RGBA16F) {
-    h4v zero;
-    zero[0] = zero[1] = zero[2] = zero[3] = static_cast<_Float16>(0.0f);
-    reinterpret_cast<h4v*>(a.out)[ao] = blend_f16(c, 1.0f, zero);
-  } else if (a.format == RT4_FRAME_RGBA8) {
-    reinterpret_cast<uint32_t*>(a.out)[ao] = blend_u8(c, 1.0f, 0u);
-  } else {
-    reinterpret_cast<float4*>(a.out)[ao] = blend_f32(c, 1.0f, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-  }
+  px_store_opaque(a.out, a.format, ao, V3{ar / wsum, ag / wsum, ab / wsum});
 }
 
 bool up_scale_ok(int32_t scale) { return scale >= 1 && scale <= RT4_UPSCALE_MAX_SCALE; }
@@ -186,56 +177,42 @@ int rt4_upscale_device(rt4_context* ctx, const rt4_uniforms* u_cells, int32_t sc
   if (u_cells->resolution[0] != static_cast<float>(cells_w) || u_cells->resolution[1] != static_cast<float>(cells_h))
     return rt4_set_err(err, errlen, "the uniforms' resolution is not the cell image's size %d x %d", cells_w, cells_h), RT4_ERR_ARG;
   const int32_t W = cells_w * scale, H = cells_h * scale;
-  if (cells_stride < cells_w || out_stride < W || (guided && (gcells_stride < cells_w || gwin_stride < W)))
-    return rt4_set_err(err, errlen, "row stride smaller than width"), RT4_ERR_ARG;
-  const RpSpan so = rp_span(d_out, out_stride, W, H, static_cast<size_t>(px_bytes));
-  const RpSpan sc = rp_span(d_cells, cells_stride, cells_w, cells_h, static_cast<size_t>(px_bytes));
-  if (so.b % px_bytes != 0 || sc.b % px_bytes != 0)
-    return rt4_set_err(err, errlen, "frame not aligned to its pixel size"), RT4_ERR_ARG;
-  bool overlap = rp_overlap(so, sc);
-  if (guided) {
-    const RpSpan sg = rp_span(d_gcells, gcells_stride, cells_w, cells_h, sizeof(rt4_gbuffer_px));
-    const RpSpan sw = rp_span(d_gwin, gwin_stride, W, H, sizeof(rt4_gbuffer_px));
-    if (sg.b % 16u != 0 || sw.b % 16u != 0) return rt4_set_err(err, errlen, "G-buffer not 16-byte aligned"), RT4_ERR_ARG;
-    overlap = overlap || rp_overlap(so, sg) || rp_overlap(so, sw);
-  }
-  if (overlap) return rt4_set_err(err, errlen, "the output overlaps an input"), RT4_ERR_ARG;
+  // nearest mode neither reads nor checks the G-buffers: they are not in the list
+  const PostImage out = post_image(d_out, out_stride, W, H, static_cast<size_t>(px_bytes), "output");
+  const PostImage in[3] = {post_image(d_cells, cells_stride, cells_w, cells_h, static_cast<size_t>(px_bytes), "cell frame"),
+                           post_image(d_gcells, gcells_stride, cells_w, cells_h, sizeof(rt4_gbuffer_px), "cell G-buffer"),
+                           post_image(d_gwin, gwin_stride, W, H, sizeof(rt4_gbuffer_px), "window G-buffer")};
+  const int st = post_check_args(&out, 1, in, guided ? 3 : 1, err, errlen);
+  if (st != RT4_OK) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int rc = order_launch(ctx, s, err, errlen);
-  if (rc != RT4_OK) return rc;
-  const dim3 grid(static_cast<unsigned>((W + UP_BX - 1) / UP_BX), static_cast<unsigned>((H + UP_BY - 1) / UP_BY)), block(256);
-  (void)hipGetLastError();
-  if (guided) {
-    UpArgs a;
-    a.cells = rp_cam(u_cells);
-    a.win = a.cells;
-    a.win.res[0] = static_cast<float>(W);  // rt4_upscale_uniforms: the products are exact
-    a.win.res[1] = static_cast<float>(H);
-    a.src = d_cells;
-    a.gcells = d_gcells;
-    a.gwin = d_gwin;
-    a.out = d_out;
-    a.src_stride = cells_stride;
-    a.gcells_stride = gcells_stride;
-    a.gwin_stride = gwin_stride;
-    a.out_stride = out_stride;
-    a.cw = cells_w;
-    a.ch = cells_h;
-    a.s = scale;
-    a.format = format;
-    a.cos_min = params->cos_min;
-    a.plane_tol = params->plane_tol;
-    hipLaunchKernelGGL(rt4_upscale_guided_kernel, grid, block, 0, s, a);
-  } else {
-    hipLaunchKernelGGL(rt4_upscale_nearest_kernel, grid, block, 0, s, d_cells, cells_stride, d_out, out_stride, format, W, H, scale);
-  }
-  const hipError_t le = hipGetLastError();
-  rc = done_launch(ctx, s, err, errlen);
-  if (le != hipSuccess) {
-    rt4_set_err(err, errlen, "upscale kernel launch failed: %s", hipGetErrorString(le));
-    return RT4_ERR_HIP;
-  }
-  return rc;
+  return post_launch(ctx, s, "upscale kernel", err, errlen, [&] {
+    const dim3 grid = px_grid(W, H), block(256);
+    if (guided) {
+      UpArgs a;
+      a.cells = rp_cam(u_cells);
+      a.win = a.cells;
+      a.win.res[0] = static_cast<float>(W);  // rt4_upscale_uniforms: the products are exact
+      a.win.res[1] = static_cast<float>(H);
+      a.src = d_cells;
+      a.gcells = d_gcells;
+      a.gwin = d_gwin;
+      a.out = d_out;
+      a.src_stride = cells_stride;
+      a.gcells_stride = gcells_stride;
+      a.gwin_stride = gwin_stride;
+      a.out_stride = out_stride;
+      a.cw = cells_w;
+      a.ch = cells_h;
+      a.s = scale;
+      a.format = format;
+      a.cos_min = params->cos_min;
+      a.plane_tol = params->plane_tol;
+      hipLaunchKernelGGL(rt4_upscale_guided_kernel, grid, block, 0, s, a);
+    } else {
+      hipLaunchKernelGGL(rt4_upscale_nearest_kernel, grid, block, 0, s, d_cells, cells_stride, d_out, out_stride, format, W, H, scale);
+    }
+    return hipGetLastError();
+  });
 }
 
 int rt4_upscale_host(rt4_context* ctx, const rt4_uniforms* u_cells, int32_t scale, const void* cells, int64_t cells_stride,
@@ -256,36 +233,21 @@ int rt4_upscale_host(rt4_context* ctx, const rt4_uniforms* u_cells, int32_t scal
   if (cells_stride < cells_w || out_stride < W || (guided && (gcells_stride < cells_w || gwin_stride < W)))
     return rt4_set_err(err, errlen, "row stride smaller than width"), RT4_ERR_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
-  // the four images in order: cells, gcells, gwin (inputs), out
-  const void* host[4] = {cells, guided ? gcells : nullptr, guided ? gwin : nullptr, out};
-  const size_t bytes[4] = {image_span(cells_stride, cells_w, cells_h) * static_cast<size_t>(px_bytes),
-                           guided ? image_span(gcells_stride, cells_w, cells_h) * sizeof(rt4_gbuffer_px) : 0u,
-                           guided ? image_span(gwin_stride, W, H) * sizeof(rt4_gbuffer_px) : 0u,
-                           image_span(out_stride, W, H) * static_cast<size_t>(px_bytes)};
-  void* d[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  for (int q = 0; q < 4 && e == hipSuccess; q++) {
-    if (!host[q]) continue;
-    e = hipMalloc(&d[q], bytes[q]);
-    if (e == hipSuccess) e = hipMemcpy(d[q], host[q], bytes[q], hipMemcpyHostToDevice);  // the output: the padding keeps its bytes
-  }
-  int st = RT4_OK;
+  HostStage dc, dgc, dgw, dout;  // nearest mode stages no G-buffer
+  hipError_t e = dc.up(cells, image_span(cells_stride, cells_w, cells_h) * static_cast<size_t>(px_bytes));
+  if (e == hipSuccess && guided) e = dgc.up(gcells, image_span(gcells_stride, cells_w, cells_h) * sizeof(rt4_gbuffer_px));
+  if (e == hipSuccess && guided) e = dgw.up(gwin, image_span(gwin_stride, W, H) * sizeof(rt4_gbuffer_px));
+  if (e == hipSuccess) e = dout.up(out, image_span(out_stride, W, H) * static_cast<size_t>(px_bytes));
   if (e == hipSuccess) {
-    st = rt4_upscale_device(ctx, u_cells, scale, d[0], cells_stride, static_cast<const rt4_gbuffer_px*>(d[1]), gcells_stride,
-                            static_cast<const rt4_gbuffer_px*>(d[2]), gwin_stride, d[3], out_stride, format, cells_w, cells_h,
-                            params, nullptr, err, errlen);
-    if (st == RT4_OK) {
-      e = hipDeviceSynchronize();
-      if (e == hipSuccess) e = hipMemcpy(out, d[3], bytes[3], hipMemcpyDeviceToHost);
-    }
+    const int st = rt4_upscale_device(ctx, u_cells, scale, dc.d, cells_stride, dgc.as<const rt4_gbuffer_px>(), gcells_stride,
+                                      dgw.as<const rt4_gbuffer_px>(), gwin_stride, dout.d, out_stride, format, cells_w, cells_h,
+                                      params, nullptr, err, errlen);
+    if (st != RT4_OK) return st;
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = dout.down(out);
   }
-  for (void* p : d)
-    if (p) (void)hipFree(p);
-  if (st == RT4_OK && e != hipSuccess) {
-    rt4_set_err(err, errlen, "upscale_host failed: %s", hipGetErrorString(e));
-    st = RT4_ERR_HIP;
-  }
-  return st;
+  if (e != hipSuccess) return rt4_set_err(err, errlen, "upscale_host failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
+  return RT4_OK;
 }
 
 // ---- rt4_window ---------------------------------------------------------------------------------------------------
@@ -325,12 +287,9 @@ int rt4_window_create(rt4_context* ctx, int32_t cells_w, int32_t cells_h, int32_
   win->format = format;
   const size_t ncells = static_cast<size_t>(cells_w) * static_cast<size_t>(cells_h);
   const size_t npx = ncells * static_cast<size_t>(scale) * static_cast<size_t>(scale);
-  hipError_t e = hipMalloc(&win->d_image, npx * static_cast<size_t>(px_bytes));
-  if (e == hipSuccess) e = hipMemset(win->d_image, 0, npx * static_cast<size_t>(px_bytes));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&win->d_gwin), npx * sizeof(rt4_gbuffer_px));
-  if (e == hipSuccess) e = hipMemset(win->d_gwin, 0, npx * sizeof(rt4_gbuffer_px));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&win->d_gcells), ncells * sizeof(rt4_gbuffer_px));
-  if (e == hipSuccess) e = hipMemset(win->d_gcells, 0, ncells * sizeof(rt4_gbuffer_px));
+  hipError_t e = alloc_zeroed(&win->d_image, npx * static_cast<size_t>(px_bytes));
+  if (e == hipSuccess) e = alloc_zeroed(reinterpret_cast<void**>(&win->d_gwin), npx * sizeof(rt4_gbuffer_px));
+  if (e == hipSuccess) e = alloc_zeroed(reinterpret_cast<void**>(&win->d_gcells), ncells * sizeof(rt4_gbuffer_px));
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
     rt4_set_err(err, errlen, "window_create failed: %s", hipGetErrorString(e));
