@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <fstream>
@@ -478,6 +479,20 @@ int rt4_band_plan(int32_t width, int32_t height, int32_t world, int32_t band, in
   return RT4_OK;
 }
 
+// Frames split over ranks in contiguous blocks (shard.py frame_split is the same arithmetic,
+// tests/test_light_merge_ref.py compares the two): the first n_frames % world ranks render one frame more.
+int rt4_frame_split(int32_t n_frames, int32_t world, int32_t rank, int32_t* first, int32_t* count, char* err,
+                    size_t errlen) {
+  if (!first || !count) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
+  if (n_frames < 0 || world < 1)
+    return rt4_set_err(err, errlen, "frame split: n_frames %d must be >= 0, world %d >= 1", n_frames, world), RT4_ERR_ARG;
+  if (rank < 0 || rank >= world) return rt4_set_err(err, errlen, "rank %d not in [0, %d)", rank, world), RT4_ERR_ARG;
+  const int32_t q = n_frames / world, r = n_frames % world;
+  *count = q + (rank < r ? 1 : 0);
+  *first = rank * q + std::min(rank, r);
+  return RT4_OK;
+}
+
 // ============================================================================ image output
 namespace {
 // One frame row as 8-bit RGB with the RGBA8 rule of rt4_frame_format (float channels clamped to [0, 1],
@@ -722,6 +737,128 @@ int rt4_accum_load(const char* path, void* frame, int32_t format, int32_t w, int
   if (rc != RT4_OK) return rc;
   if (frames_done) *frames_done = hd.frames_done;
   if (seed) *seed = hd.seed;
+  return RT4_OK;
+}
+
+// ============================================================================ light accumulator checkpoint
+namespace {
+constexpr char kLitMagic[8] = {'R', 'T', '4', 'L', 'I', 'T', '1', '\0'};
+struct LitHeader {  // the file's first 48 bytes (rt4.h), little-endian like every supported host
+  char magic[8];
+  int32_t version, w, h;
+  int32_t frames_issued_w[2];  // int64 frames_issued at byte 20: two words, so that the struct has no padding
+  uint32_t seed, key, flags, zero;
+  uint32_t pad_;  // not in the file: sizeof is 48 with it, the file's header is the first 44 bytes
+};
+constexpr size_t kLitHeaderBytes = 44;
+static_assert(offsetof(LitHeader, pad_) == kLitHeaderBytes, "light checkpoint header layout");
+
+struct LitInfo {
+  int32_t w, h;
+  int64_t frames_issued;
+  uint32_t seed, key, flags;
+};
+
+// The header, checked against the file's size: f is left at the first pixel.
+int lit_read_header(std::FILE* f, const char* path, LitInfo& info, char* err, size_t errlen) {
+  LitHeader hd{};
+  if (std::fread(&hd, 1, kLitHeaderBytes, f) != kLitHeaderBytes || std::memcmp(hd.magic, kLitMagic, sizeof kLitMagic) != 0)
+    return rt4_set_err(err, errlen, "%s is not an rt4 light checkpoint", path), RT4_ERR_PARSE;
+  if (hd.version != RT4_LIGHT_FILE_VERSION)
+    return rt4_set_err(err, errlen, "%s: light checkpoint version %d, expected %d", path, hd.version, RT4_LIGHT_FILE_VERSION),
+           RT4_ERR_PARSE;
+  std::memcpy(&info.frames_issued, hd.frames_issued_w, sizeof info.frames_issued);
+  if (hd.w <= 0 || hd.h <= 0 || info.frames_issued < 0 || hd.zero != 0u)
+    return rt4_set_err(err, errlen, "%s: bad light checkpoint header", path), RT4_ERR_PARSE;
+  const long long want = static_cast<long long>(kLitHeaderBytes) +
+                         static_cast<long long>(hd.w) * hd.h * static_cast<long long>(sizeof(rt4_light_px));
+  long long have = -1;
+  if (std::fseek(f, 0, SEEK_END) == 0) have = std::ftell(f);
+  if (have != want || std::fseek(f, static_cast<long>(kLitHeaderBytes), SEEK_SET) != 0)
+    return rt4_set_err(err, errlen, "%s: %lld bytes, the header's %d x %d pixels need %lld (truncated?)", path, have, hd.w,
+                       hd.h, want),
+           RT4_ERR_PARSE;
+  info.w = hd.w;
+  info.h = hd.h;
+  info.seed = hd.seed;
+  info.key = hd.key;
+  info.flags = hd.flags;
+  return RT4_OK;
+}
+}  // namespace
+
+int rt4_light_save(const char* path, const rt4_light_px* light, int32_t w, int32_t h, int64_t row_stride_px,
+                   int64_t frames_issued, uint32_t seed, uint32_t key, uint32_t flags, char* err, size_t errlen) {
+  if (!path || !light || w <= 0 || h <= 0 || row_stride_px < w || frames_issued < 0)
+    return rt4_set_err(err, errlen, "bad argument"), RT4_ERR_ARG;
+  LitHeader hd{};
+  std::memcpy(hd.magic, kLitMagic, sizeof kLitMagic);
+  hd.version = RT4_LIGHT_FILE_VERSION;
+  hd.w = w;
+  hd.h = h;
+  std::memcpy(hd.frames_issued_w, &frames_issued, sizeof frames_issued);
+  hd.seed = seed;
+  hd.key = key;
+  hd.flags = flags;
+  // as rt4_accum_save_key: next to the target, flushed to the disk, then renamed over it
+  const std::string tmp = std::string(path) + ".tmp";
+  std::FILE* f = std::fopen(tmp.c_str(), "wb");
+  if (!f) return rt4_set_err(err, errlen, "cannot open %s for writing", tmp.c_str()), RT4_ERR_IO;
+  bool ok = std::fwrite(&hd, 1, kLitHeaderBytes, f) == kLitHeaderBytes;
+  const size_t row = static_cast<size_t>(w) * sizeof(rt4_light_px);
+  for (int32_t i = 0; ok && i < h; i++) ok = std::fwrite(light + static_cast<size_t>(i) * row_stride_px, 1, row, f) == row;
+  ok = ok && std::fflush(f) == 0 && fsync(fileno(f)) == 0;
+  if (std::fclose(f) != 0) ok = false;
+  if (ok && std::rename(tmp.c_str(), path) != 0) ok = false;
+  if (!ok) {
+    std::remove(tmp.c_str());
+    return rt4_set_err(err, errlen, "write failed: %s", path), RT4_ERR_IO;
+  }
+  return RT4_OK;
+}
+
+int rt4_light_info(const char* path, int32_t* w, int32_t* h, int64_t* frames_issued, uint32_t* seed, uint32_t* key,
+                   uint32_t* flags, char* err, size_t errlen) {
+  if (!path) return rt4_set_err(err, errlen, "bad argument"), RT4_ERR_ARG;
+  std::FILE* f = std::fopen(path, "rb");
+  if (!f) return rt4_set_err(err, errlen, "cannot open %s", path), RT4_ERR_IO;
+  LitInfo info{};
+  const int rc = lit_read_header(f, path, info, err, errlen);
+  std::fclose(f);
+  if (rc != RT4_OK) return rc;
+  if (w) *w = info.w;
+  if (h) *h = info.h;
+  if (frames_issued) *frames_issued = info.frames_issued;
+  if (seed) *seed = info.seed;
+  if (key) *key = info.key;
+  if (flags) *flags = info.flags;
+  return RT4_OK;
+}
+
+int rt4_light_load(const char* path, rt4_light_px* light, int32_t w, int32_t h, int64_t row_stride_px,
+                   int64_t* frames_issued, uint32_t* seed, uint32_t* key, uint32_t* flags, char* err, size_t errlen) {
+  if (!path || !light || w <= 0 || h <= 0 || row_stride_px < w) return rt4_set_err(err, errlen, "bad argument"), RT4_ERR_ARG;
+  std::FILE* f = std::fopen(path, "rb");
+  if (!f) return rt4_set_err(err, errlen, "cannot open %s", path), RT4_ERR_IO;
+  LitInfo info{};
+  int rc = lit_read_header(f, path, info, err, errlen);
+  if (rc == RT4_OK && (info.w != w || info.h != h)) {
+    rt4_set_err(err, errlen, "%s holds a %dx%d light accumulator, not %dx%d", path, info.w, info.h, w, h);
+    rc = RT4_ERR_ARG;
+  }
+  // the size was checked with the header, so a short read here is an I/O error; rows read so far stay
+  const size_t row = static_cast<size_t>(w) * sizeof(rt4_light_px);
+  for (int32_t i = 0; rc == RT4_OK && i < h; i++)
+    if (std::fread(light + static_cast<size_t>(i) * row_stride_px, 1, row, f) != row) {
+      rt4_set_err(err, errlen, "%s: read failed (row %d of %d)", path, i, h);
+      rc = RT4_ERR_IO;
+    }
+  std::fclose(f);
+  if (rc != RT4_OK) return rc;
+  if (frames_issued) *frames_issued = info.frames_issued;
+  if (seed) *seed = info.seed;
+  if (key) *key = info.key;
+  if (flags) *flags = info.flags;
   return RT4_OK;
 }
 

@@ -2,7 +2,7 @@
 // rt4_light_noise_device): kernels and entry points. From rt4_post.h: the argument checks, the launch
 // bracket, the pixel grid, px_store_opaque and HostStage; from no other pass (KernelArgs, launch_jobs and TileList are
 // rt4_trace.hip's). rt4_light_denoise.h and rt4_light_tiles.h take light_tone, light_apply, LIGHT_LOAD_BATCH and
-// render_light / render_light_staged from here. No trace kernel uses anything from here.
+// render_light / render_light_staged from here, rt4_light_merge.h light_image. No trace kernel uses anything from here.
 //
 // The trace kernels already hand every frame's raw light sum to the frame-colour scratch (KernelArgs::fcolor); the
 // colour accumulators tone-map it in rt4_fold_frames_kernel. The light accumulator is a second fold over the same

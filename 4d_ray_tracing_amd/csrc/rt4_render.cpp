@@ -40,7 +40,25 @@
 //                   at the end, for the threshold Q in display units (default 1/255, one 8-bit step); --noise-map: also
 //                   <prefix>_<section>_q.<ext>, the display error q as grey. An error estimate, not a stop rule: on
 //                   scenes lit by small emitters `above` rises over the first hundred frames. --denoise and --window
-//                   work on the resolved image. Not with --reproject, --resume, --checkpoint, --gpus, --frame-by-frame)
+//                   work on the resolved image; with --raw also <prefix>_<section>_light.raw, the accumulator's bytes. Not
+//                   with --reproject, --frame-by-frame, nor with --resume, --checkpoint, --gpus: those are the colour
+//                   path's and its file format's; the light path has the three flags below)
+//                   [--light-checkpoint F] [--light-resume F]  (need --light, one section: save the light accumulator,
+//                   rt4_light_save, with the last frame number issued, the seed and the run's key / continue one with
+//                   frame frames_issued + 1, -n more frames: the bytes of an unbroken run. A resume refuses another
+//                   --seed, scene, properties, camera or size, a pooled file, and --adaptive, whose pass state the file
+//                   does not hold; --adaptive with --light-checkpoint is fine)
+//                   [--light-gpus N [--light-split frames|bands] [--band B] [--rehearse]]  (needs --light, one section, not
+//                   with --adaptive or --light-resume, N <= 16. frames, the default: rt4_frame_split, rank r renders the
+//                   whole image for its block of the frame numbers, one gather, one rt4_light_merge_device of the N
+//                   accumulators into the root's empty one; every rank's launch is as large as the one-GPU launch, so it
+//                   scales at window sizes where bands cannot fill a GPU, and the result is as accurate as the one-GPU
+//                   accumulator but not bit-equal. bands: the bands of --gpus, rt4_light_bands_unpermute_device: bit-equal.
+//                   Resolve, statistics, --noise-map, --light-denoise, --denoise and --window run on the root's
+//                   accumulator; --rehearse and the RT4_RENDER_FAIL_* hooks as with --gpus)
+//                   [--light-pool A B [C ...]]  (renders nothing: loads light checkpoints of runs that differ only in
+//                   --seed, refuses another key or size and a seed twice, merges them in order, rt4_light_merge_host, and
+//                   writes the resolve, the statistics and, with --light-checkpoint, a pooled file, which cannot be resumed)
 //                   [--light-denoise [levels]]  (needs --light: next to every image also <name>_ldn.<ext>, the light
 //                   accumulator through the variance-guided filter, rt4_render_gbuffer_device of the section's pose +
 //                   rt4_light_denoise_device, tone-mapped once at the end; with --window the filtered frame is the one
@@ -64,6 +82,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -138,25 +157,40 @@ class Agreement {
   Barrier& bar_;
 };
 
-// The frames of one section on `gpus` devices: pixel bands dealt round-robin
+// What a multi-GPU run is made of besides the machinery of render_shards: the size of every rank's shard and of
+// the root's image, the rank's own set-up, its render call and the root's last step. Three runs fill it in:
+// --gpus (colour frames in pixel bands), --light-gpus --light-split bands (a light accumulator in the same bands)
+// and --light-gpus --light-split frames (whole-image light accumulators of disjoint frame blocks, merged).
+struct ShardJob {
+  const char* flag;                  // "--gpus" / "--light-gpus": names the run in error messages
+  size_t shard_bytes, image_bytes;   // every rank's shard (equal sizes: one gather); the root's result
+  // rank r's set-up on its context, after its allocations (false: err holds the reason)
+  std::function<bool(int r, rt4_context* ctx, char* err, size_t errlen)> setup;
+  // rank r's renders into its zeroed shard, enqueued on stream (an RT4 status)
+  std::function<int(int r, rt4_context* ctx, void* shard, unsigned long long* d_count, hipStream_t stream, char* err,
+                    size_t errlen)> render;
+  // the root's last step: the gathered shards (rank-major) into the zeroed image (an RT4 status)
+  std::function<int(rt4_context* ctx, const void* gathered, void* image, hipStream_t stream, char* err, size_t errlen)> finish;
+};
+
+// One section on `gpus` devices: every rank renders its shard (job.render), one ncclGather of the
+// shards to rank 0, and the root's last step there (job.finish). For --gpus that is: pixel bands dealt round-robin
 // (rt4_band_plan), each rank's frames pipelined in one rt4_render_frames_device call into a padded
-// shard of rows_max rows, one ncclGather of the shards to rank 0 and rt4_bands_unpermute_device there.
+// shard of rows_max rows, and rt4_bands_unpermute_device on the root.
 // The image equals a one-GPU render bit for bit (every pixel is independent: shader.frag:104-108).
 //
 // rehearse (--rehearse, a test switch for boxes with one GPU): every rank is a host thread with its own
 // context, stream and buffers on device 0, and each rank copies its shard into its slot of rank 0's
-// gathered buffer with hipMemcpyAsync where the real run calls ncclGather; the band plan, the barrier,
-// the agreements and the un-permute are the real ones. fail_rank >= 0 (the RT4_RENDER_FAIL_RANK test hook)
+// gathered buffer with hipMemcpyAsync where the real run calls ncclGather; the plan, the barrier,
+// the agreements and the last step are the real ones. fail_rank >= 0 (the RT4_RENDER_FAIL_RANK test hook)
 // makes that rank's set-up fail after its allocations, or with fail_gather (RT4_RENDER_FAIL_STAGE=gather) its
 // gather: the rank does not enqueue its part of the collective and reports an error, as when ncclGather fails.
 // After the gather is enqueued the ranks agree once more: if any rank failed, every rank aborts its communicator
 // (ncclCommAbort), so no rank waits forever in a collective its peer never joined. While the gather runs, every
 // rank also watches its communicator's asynchronous error (ncclCommGetAsyncError) and a shared abort flag.
-// Returns the frame on the host (rank 0's), or exits with status 1 naming the failed rank(s).
-std::vector<unsigned char> render_bands(int gpus, int band, const rt4_scene_desc* scene, const std::vector<rt4_uniforms>& us,
-                                        int32_t w, int32_t h, int32_t format, bool frame_by_frame, bool rehearse,
-                                        int fail_rank, bool fail_gather, unsigned long long* count_out, double* ms_out) {
-  const int32_t px = rt4_frame_format_bytes(format);
+// Returns the root's result on the host (rank 0's), or exits with status 1 naming the failed rank(s).
+std::vector<unsigned char> render_shards(int gpus, const rt4_scene_desc* scene, const ShardJob& job, bool rehearse,
+                                         int fail_rank, bool fail_gather, unsigned long long* count_out, double* ms_out) {
   std::vector<ncclComm_t> comms(static_cast<size_t>(gpus), nullptr);
   if (!rehearse) {
     std::vector<int> devs(static_cast<size_t>(gpus));
@@ -164,7 +198,8 @@ std::vector<unsigned char> render_bands(int gpus, int band, const rt4_scene_desc
     if (ncclCommInitAll(comms.data(), gpus, devs.data()) != ncclSuccess) die("ncclCommInitAll", "failed");
   }
   std::vector<BandRun> runs(static_cast<size_t>(gpus));
-  std::vector<unsigned char> image(static_cast<size_t>(w) * h * px);
+  std::vector<unsigned char> image(job.image_bytes);
+  const size_t shard_bytes = job.shard_bytes;
   Barrier bar(gpus);
   Agreement agree(gpus, bar);
   void* root_gathered = nullptr;  // rank 0's gathered buffer (rehearse: the other ranks copy into it)
@@ -176,8 +211,6 @@ std::vector<unsigned char> render_bands(int gpus, int band, const rt4_scene_desc
     void *shard = nullptr, *gathered = nullptr, *img = nullptr;
     unsigned long long* d_count = nullptr;
     hipStream_t stream = nullptr;
-    rt4_region reg{0, 0, 0, 0, 0, 0};
-    int32_t rows_max = 0;
     const int dev = rehearse ? 0 : r;
     auto fail = [&](const char* what) {
       if (run.error.empty()) run.error = what;
@@ -185,39 +218,26 @@ std::vector<unsigned char> render_bands(int gpus, int band, const rt4_scene_desc
     };
     bool ok = (hipSetDevice(dev) == hipSuccess && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess) ||
               fail("hipSetDevice / hipStreamCreate");
-    if (ok && (rt4_band_plan(w, h, gpus, band, r, &reg, &rows_max, err, sizeof err) != RT4_OK ||
-               rt4_context_create(dev, RT4_FLAG_SAMPLER_LUT, &ctx, err, sizeof err) != RT4_OK ||
+    if (ok && (rt4_context_create(dev, RT4_FLAG_SAMPLER_LUT, &ctx, err, sizeof err) != RT4_OK ||
                rt4_context_set_scene(ctx, scene, err, sizeof err) != RT4_OK))
       ok = fail(err);
-    const size_t shard_bytes = static_cast<size_t>(rows_max) * w * px;
     if (ok) {
       ok = (hipMalloc(&shard, shard_bytes) == hipSuccess && hipMemset(shard, 0, shard_bytes) == hipSuccess &&
             hipMalloc(&d_count, sizeof *d_count) == hipSuccess && hipMemset(d_count, 0, sizeof *d_count) == hipSuccess) ||
            fail("device allocation");
       if (ok && r == 0)
-        ok = (hipMalloc(&gathered, shard_bytes * gpus) == hipSuccess && hipMalloc(&img, image.size()) == hipSuccess) ||
+        ok = (hipMalloc(&gathered, shard_bytes * gpus) == hipSuccess && hipMalloc(&img, image.size()) == hipSuccess &&
+              hipMemset(img, 0, image.size()) == hipSuccess) ||
              fail("device allocation");
     }
-    const bool pipelined = ok && !frame_by_frame && us.size() >= 2 && reg.h > 0 &&
-                           rt4_context_frames_per_launch(ctx, reg.w, reg.h) > 1;
-    if (ok && pipelined && rt4_context_reserve_frames(ctx, reg.w, reg.h, err, sizeof err) != RT4_OK) ok = fail(err);
+    if (ok && !job.setup(r, ctx, err, sizeof err)) ok = fail(err);
     if (ok && r == fail_rank && !fail_gather) ok = fail("set-up failure injected (RT4_RENDER_FAIL_RANK)");
     if (ok) ok = hipDeviceSynchronize() == hipSuccess || fail("hipDeviceSynchronize");
     if (r == 0) root_gathered = gathered;  // read by the other ranks only after the agreement's barrier
     // every rank set up (the agreement is also the start barrier): otherwise nobody renders or gathers
     const bool all_set = agree.all(r, ok);
     const auto t0 = std::chrono::steady_clock::now();
-    if (all_set && reg.h > 0) {
-      int st = RT4_OK;
-      if (pipelined) {
-        st = rt4_render_frames_device(ctx, us.data(), static_cast<int32_t>(us.size()), &reg, shard, format, w, d_count,
-                                      stream, err, sizeof err);
-      } else {
-        for (size_t f = 0; f < us.size() && st == RT4_OK; f++)
-          st = rt4_render_device_ex(ctx, &us[f], &reg, shard, format, w, d_count, stream, err, sizeof err);
-      }
-      if (st != RT4_OK) ok = fail(err);
-    }
+    if (all_set && job.render(r, ctx, shard, d_count, stream, err, sizeof err) != RT4_OK) ok = fail(err);
     // the renders were enqueued everywhere: only then the collective (a launch error skips it on every rank)
     const bool all_rendered = all_set && agree.all(r, ok);
     bool all_gathered = false;
@@ -257,9 +277,7 @@ std::vector<unsigned char> render_bands(int gpus, int band, const rt4_scene_desc
         comms[static_cast<size_t>(r)] = nullptr;
         if (ok) ok = fail("communicator aborted: another rank failed in the gather");
       }
-      if (ok && !abort_all && r == 0 &&
-          rt4_bands_unpermute_device(gathered, img, w, h, gpus, band, rows_max, format, stream, err, sizeof err) != RT4_OK)
-        ok = fail(err);
+      if (ok && !abort_all && r == 0 && job.finish(ctx, gathered, img, stream, err, sizeof err) != RT4_OK) ok = fail(err);
     }
     if (stream && hipStreamSynchronize(stream) != hipSuccess && !abort_all) ok = fail("hipStreamSynchronize");
     run.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -288,10 +306,116 @@ std::vector<unsigned char> render_bands(int gpus, int band, const rt4_scene_desc
     count += run.count;
     ms = std::max(ms, run.ms);  // the job's time: the slowest rank
   }
-  if (!errors.empty()) die("--gpus", errors.c_str());
+  if (!errors.empty()) die(job.flag, errors.c_str());
   *count_out = count;
   *ms_out = ms;
   return image;
+}
+
+// The band plan of every rank (rt4_band_plan), shared by the two band-split jobs below.
+struct BandPlans {
+  std::vector<rt4_region> reg;
+  int32_t rows_max = 0;
+  BandPlans(int gpus, int band, int32_t w, int32_t h, const char* flag) : reg(static_cast<size_t>(gpus)) {
+    char err[1024] = {0};
+    for (int r = 0; r < gpus; r++)
+      if (rt4_band_plan(w, h, gpus, band, r, &reg[static_cast<size_t>(r)], &rows_max, err, sizeof err) != RT4_OK) die(flag, err);
+  }
+};
+
+// --gpus: the colour frames of one section in pixel bands.
+std::vector<unsigned char> render_bands(int gpus, int band, const rt4_scene_desc* scene, const std::vector<rt4_uniforms>& us,
+                                        int32_t w, int32_t h, int32_t format, bool frame_by_frame, bool rehearse,
+                                        int fail_rank, bool fail_gather, unsigned long long* count_out, double* ms_out) {
+  const size_t px = static_cast<size_t>(rt4_frame_format_bytes(format));
+  const BandPlans plan(gpus, band, w, h, "--gpus");
+  std::vector<char> pipelined(static_cast<size_t>(gpus), 0);
+  ShardJob job;
+  job.flag = "--gpus";
+  job.shard_bytes = static_cast<size_t>(plan.rows_max) * w * px;
+  job.image_bytes = static_cast<size_t>(w) * h * px;
+  job.setup = [&](int r, rt4_context* ctx, char* err, size_t errlen) {
+    const rt4_region& reg = plan.reg[static_cast<size_t>(r)];
+    pipelined[static_cast<size_t>(r)] =
+        !frame_by_frame && us.size() >= 2 && reg.h > 0 && rt4_context_frames_per_launch(ctx, reg.w, reg.h) > 1;
+    return !pipelined[static_cast<size_t>(r)] || rt4_context_reserve_frames(ctx, reg.w, reg.h, err, errlen) == RT4_OK;
+  };
+  job.render = [&](int r, rt4_context* ctx, void* shard, unsigned long long* d_count, hipStream_t stream, char* err,
+                   size_t errlen) {
+    const rt4_region& reg = plan.reg[static_cast<size_t>(r)];
+    int st = RT4_OK;
+    if (reg.h <= 0) return st;
+    if (pipelined[static_cast<size_t>(r)]) {
+      st = rt4_render_frames_device(ctx, us.data(), static_cast<int32_t>(us.size()), &reg, shard, format, w, d_count, stream,
+                                    err, errlen);
+    } else {
+      for (size_t f = 0; f < us.size() && st == RT4_OK; f++)
+        st = rt4_render_device_ex(ctx, &us[f], &reg, shard, format, w, d_count, stream, err, errlen);
+    }
+    return st;
+  };
+  job.finish = [&](rt4_context*, const void* gathered, void* image, hipStream_t stream, char* err, size_t errlen) {
+    return rt4_bands_unpermute_device(gathered, image, w, h, gpus, band, plan.rows_max, format, stream, err, errlen);
+  };
+  return render_shards(gpus, scene, job, rehearse, fail_rank, fail_gather, count_out, ms_out);
+}
+
+// --light-gpus: the light accumulator of one section. bands: the accumulator's pixels in the bands of --gpus, every rank
+// all frames of its bands, rt4_light_bands_unpermute_device on the root: bit for bit the one-GPU accumulator. frames:
+// every rank the whole image for its block of the frame numbers (rt4_frame_split; a rank without frames leaves its
+// shard empty), one rt4_light_merge_device of all ranks' accumulators into the root's empty one: as accurate as the
+// one-GPU accumulator, not bit-equal to it. us[n - 1] holds the uniforms of frame n.
+std::vector<unsigned char> render_light_shards(int gpus, bool split_bands, int band, const rt4_scene_desc* scene,
+                                               const std::vector<rt4_uniforms>& us, int32_t w, int32_t h, bool rehearse,
+                                               int fail_rank, bool fail_gather, unsigned long long* count_out,
+                                               double* ms_out) {
+  const size_t px = sizeof(rt4_light_px);
+  const int32_t n_frames = static_cast<int32_t>(us.size());
+  ShardJob job;
+  job.flag = "--light-gpus";
+  job.image_bytes = static_cast<size_t>(w) * h * px;
+  if (split_bands) {
+    const BandPlans plan(gpus, band, w, h, "--light-gpus");
+    job.shard_bytes = static_cast<size_t>(plan.rows_max) * w * px;
+    job.setup = [&](int r, rt4_context* ctx, char* err, size_t errlen) {
+      const rt4_region& reg = plan.reg[static_cast<size_t>(r)];
+      return reg.h <= 0 || rt4_context_reserve_frames(ctx, reg.w, reg.h, err, errlen) == RT4_OK;
+    };
+    job.render = [&](int r, rt4_context* ctx, void* shard, unsigned long long* d_count, hipStream_t stream, char* err,
+                     size_t errlen) {
+      const rt4_region& reg = plan.reg[static_cast<size_t>(r)];
+      if (reg.h <= 0) return static_cast<int>(RT4_OK);
+      return rt4_render_light_device(ctx, us.data(), n_frames, &reg, static_cast<rt4_light_px*>(shard), w, d_count, stream,
+                                     err, errlen);
+    };
+    job.finish = [&](rt4_context*, const void* gathered, void* image, hipStream_t stream, char* err, size_t errlen) {
+      return rt4_light_bands_unpermute_device(static_cast<const rt4_light_px*>(gathered), static_cast<rt4_light_px*>(image), w,
+                                              h, gpus, band, plan.rows_max, stream, err, errlen);
+    };
+    return render_shards(gpus, scene, job, rehearse, fail_rank, fail_gather, count_out, ms_out);
+  }
+  const rt4_region whole{0, 0, w, h, 0, 0};
+  std::vector<int32_t> first(static_cast<size_t>(gpus)), count(static_cast<size_t>(gpus));
+  char perr[1024] = {0};
+  for (int r = 0; r < gpus; r++)
+    if (rt4_frame_split(n_frames, gpus, r, &first[static_cast<size_t>(r)], &count[static_cast<size_t>(r)], perr, sizeof perr) !=
+        RT4_OK)
+      die("--light-gpus", perr);
+  job.shard_bytes = job.image_bytes;
+  job.setup = [&](int r, rt4_context* ctx, char* err, size_t errlen) {
+    return count[static_cast<size_t>(r)] == 0 || rt4_context_reserve_frames(ctx, w, h, err, errlen) == RT4_OK;
+  };
+  job.render = [&](int r, rt4_context* ctx, void* shard, unsigned long long* d_count, hipStream_t stream, char* err,
+                   size_t errlen) {
+    if (count[static_cast<size_t>(r)] == 0) return static_cast<int>(RT4_OK);
+    return rt4_render_light_device(ctx, us.data() + first[static_cast<size_t>(r)], count[static_cast<size_t>(r)], &whole,
+                                   static_cast<rt4_light_px*>(shard), w, d_count, stream, err, errlen);
+  };
+  job.finish = [&](rt4_context* ctx, const void* gathered, void* image, hipStream_t stream, char* err, size_t errlen) {
+    return rt4_light_merge_device(ctx, static_cast<rt4_light_px*>(image), w, static_cast<const rt4_light_px*>(gathered), w,
+                                  static_cast<int64_t>(w) * h, gpus, w, h, stream, err, errlen);
+  };
+  return render_shards(gpus, scene, job, rehearse, fail_rank, fail_gather, count_out, ms_out);
 }
 
 void write_raw(const std::string& path, const std::vector<unsigned char>& bytes) {  // --raw
@@ -344,6 +468,12 @@ int main(int argc, char** argv) {
   int ad_warmup = 8, ad_pass = 4, ad_full_every = 4;  // --adaptive-warmup / --adaptive-pass / --adaptive-full-every
   rt4_tile_select_params ad_select;                   // --adaptive-min-above / --adaptive-dilate; threshold: --noise-threshold
   rt4_tile_select_params_default(&ad_select);
+  // --light-resume / --light-checkpoint / --light-gpus / --light-pool: the light path's own restart,
+  // multi-GPU and pooling flags; --resume, --checkpoint and --gpus stay the colour path's
+  std::string light_resume_path, light_checkpoint_path, light_split = "frames";
+  bool light_split_given = false;
+  int light_gpus = 0;
+  std::vector<std::string> light_pool;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -374,6 +504,15 @@ int main(int argc, char** argv) {
     else if (a == "--light") light = true;
     else if (a == "--noise-map") noise_map = true;
     else if (a == "--noise-threshold") noise_threshold = static_cast<float>(std::atof(next()));
+    else if (a == "--light-resume") light_resume_path = next();
+    else if (a == "--light-checkpoint") light_checkpoint_path = next();
+    else if (a == "--light-gpus") light_gpus = std::atoi(next());
+    else if (a == "--light-split") light_split = next(), light_split_given = true;
+    else if (a == "--light-pool") {  // every following argument up to the next flag
+      while (i + 1 < argc && argv[i + 1][0] != '-') light_pool.push_back(argv[++i]);
+      if (light_pool.size() < 2) die("--light-pool", "needs two or more light checkpoints");
+      light = true;
+    }
     else if (a == "--adaptive") adaptive = true;
     else if (a == "--adaptive-warmup") ad_warmup = std::atoi(next()), ad_given = true;
     else if (a == "--adaptive-pass") ad_pass = std::atoi(next()), ad_given = true;
@@ -414,8 +553,24 @@ int main(int argc, char** argv) {
   if (reproject && frame_by_frame) die("--reproject", "not with --frame-by-frame: every temporal frame is a launch of its own");
   if (light && reproject) die("--light", "not with --reproject: the temporal history is a colour average");
   if (light && (!resume_path.empty() || !checkpoint_path.empty()))
-    die("--light", "not with --resume / --checkpoint: a checkpoint holds colours, not a light accumulator");
-  if (light && gpus > 0) die("--light", "not with --gpus: the light accumulator is not gathered");
+    die("--light", "not with --resume / --checkpoint: a checkpoint holds colours, not a light accumulator "
+                   "(--light-resume / --light-checkpoint save and continue a light accumulator)");
+  if (light && gpus > 0)
+    die("--light", "not with --gpus: that gathers colour frames (--light-gpus N runs a light accumulator on N GPUs)");
+  const bool pool = !light_pool.empty();
+  if ((!light_resume_path.empty() || !light_checkpoint_path.empty() || light_gpus != 0 || light_split_given) && !light)
+    die("--light-resume / --light-checkpoint / --light-gpus / --light-split", "need --light");
+  if (light_split_given && light_gpus == 0) die("--light-split", "needs --light-gpus");
+  if (light_split != "frames" && light_split != "bands") die("--light-split", "frames or bands");
+  if (light_gpus != 0 && (light_gpus < 1 || light_gpus > RT4_LIGHT_MERGE_MAX))
+    die("--light-gpus", "N must be 1..16 (RT4_LIGHT_MERGE_MAX: one merge takes that many accumulators)");
+  if (light_gpus > 0 && adaptive) die("--light-gpus", "not with --adaptive: the tile selection runs on one GPU");
+  if (light_gpus > 0 && !light_resume_path.empty()) die("--light-gpus", "not with --light-resume: resume on one GPU");
+  if (!light_resume_path.empty() && adaptive)
+    die("--light-resume", "not with --adaptive: a light checkpoint does not hold the adaptive loop's pass state");
+  if (pool && (adaptive || light_gpus > 0 || !light_resume_path.empty() || three || denoise_levels > 0 ||
+               light_denoise_levels >= 0 || window_scale != 0 || reproject))
+    die("--light-pool", "renders nothing: only with -o, --png, --raw, --noise-map, --noise-threshold, --light-checkpoint");
   if (light && frame_by_frame) die("--light", "not with --frame-by-frame: the frames go through rt4_render_light_device");
   if (light && keys && move_seconds > 0.0f) die("--light", "needs a resting camera: the accumulator averages one view");
   if ((noise_map || noise_threshold != 1.0f / 255.0f) && !light) die("--noise-map / --noise-threshold", "need --light");
@@ -493,6 +648,60 @@ int main(int argc, char** argv) {
     if (ck_key != 0u && ck_key != run_key)
       die("--resume", "the checkpoint was made with another scene, properties or camera");
     cam.frame_number = static_cast<uint32_t>(frames_done + 1);
+  }
+  // --light-resume: the accumulator the run continues (frames frames_done + 1 ...); --light-pool: the accumulators of
+  // independent runs, merged once there is a context. Both are refused rather than mixed with another run's frames.
+  if ((!light_resume_path.empty() || !light_checkpoint_path.empty()) && three)
+    die("--light-resume / --light-checkpoint", "need one section");
+  std::vector<rt4_light_px> light_start;  // --light-resume: the loaded accumulator; --light-pool: every file's, in order
+  uint32_t pool_seed = 0, pool_key = 0;
+  int64_t pool_issued = 0;
+  if (!light_resume_path.empty()) {
+    uint32_t ck_seed = 0, ck_key = 0, ck_flags = 0;
+    int32_t ck_w = 0, ck_h = 0;
+    RT4_CHECK(rt4_light_info(light_resume_path.c_str(), &ck_w, &ck_h, nullptr, &ck_seed, &ck_key, &ck_flags, err, sizeof err));
+    if (ck_flags & RT4_LIGHT_POOLED) die("--light-resume", "the checkpoint pools runs of several seeds: it cannot be resumed");
+    if (ck_w != cw[0] || ck_h != ch[0])
+      die("--light-resume", ("the checkpoint holds a " + std::to_string(ck_w) + "x" + std::to_string(ck_h) + " accumulator, not " +
+                             std::to_string(cw[0]) + "x" + std::to_string(ch[0])).c_str());
+    if (ck_seed != seed) die("--light-resume", "the checkpoint was made with another --seed");
+    if (ck_key != 0u && ck_key != run_key)
+      die("--light-resume", "the checkpoint was made with another scene, properties or camera");
+    light_start.resize(static_cast<size_t>(cw[0]) * ch[0]);
+    RT4_CHECK(rt4_light_load(light_resume_path.c_str(), light_start.data(), cw[0], ch[0], cw[0], &frames_done, nullptr, nullptr,
+                             nullptr, err, sizeof err));
+    if (frames_done + frames > 0xFFFFFFFFll) die("--light-resume", "frame numbers beyond 2^32 - 1");
+    cam.frame_number = static_cast<uint32_t>(frames_done + 1);
+  }
+  if (pool) {
+    std::vector<uint32_t> seeds;
+    for (size_t s = 0; s < light_pool.size(); s++) {
+      int32_t fw = 0, fh = 0;
+      int64_t issued = 0;
+      uint32_t ck_seed = 0, ck_key = 0;
+      RT4_CHECK(rt4_light_info(light_pool[s].c_str(), &fw, &fh, &issued, &ck_seed, &ck_key, nullptr, err, sizeof err));
+      if (s == 0) {
+        cw[0] = fw, ch[0] = fh, pool_seed = ck_seed, pool_key = ck_key, pool_issued = issued;
+        light_start.resize(light_pool.size() * static_cast<size_t>(fw) * fh);
+      }
+      if (fw != cw[0] || fh != ch[0]) die("--light-pool: another image size than the first file's", light_pool[s].c_str());
+      if (ck_key != pool_key) die("--light-pool: another scene, properties or camera than the first file's", light_pool[s].c_str());
+      if (std::find(seeds.begin(), seeds.end(), ck_seed) != seeds.end())
+        die("--light-pool: the same --seed as an earlier file, the same frames would count twice", light_pool[s].c_str());
+      seeds.push_back(ck_seed);
+      RT4_CHECK(rt4_light_load(light_pool[s].c_str(), light_start.data() + s * static_cast<size_t>(fw) * fh, fw, fh, fw, nullptr,
+                               nullptr, nullptr, nullptr, err, sizeof err));
+    }
+    frames = 0;  // nothing is rendered
+  }
+  if (light_gpus > 0) {  // as --gpus: one section (the camera rests in every --light run)
+    if (three) die("--light-gpus", "needs one section");
+    if (frames < 1 || band < 1) die("--light-gpus", "frames and band must be >= 1");
+    if (!rehearse) {
+      int ndev = 0;
+      HIP_CHECK(hipGetDeviceCount(&ndev));
+      if (light_gpus > ndev) die("--light-gpus", ("only " + std::to_string(ndev) + " HIP devices").c_str());
+    }
   }
 
   if (gpus > 0 && denoise_levels > 0) die("--denoise", "not with --gpus: the frame is not filtered after the gather");
@@ -582,6 +791,25 @@ int main(int argc, char** argv) {
     HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_light[q]), static_cast<size_t>(cw[q]) * ch[q] * sizeof(rt4_light_px)));
     HIP_CHECK(hipMemset(d_light[q], 0, static_cast<size_t>(cw[q]) * ch[q] * sizeof(rt4_light_px)));  // empty
   }
+  const size_t light_bytes0 = static_cast<size_t>(cw[0]) * ch[0] * sizeof(rt4_light_px);
+  if (!light_resume_path.empty()) HIP_CHECK(hipMemcpy(d_light[0], light_start.data(), light_bytes0, hipMemcpyHostToDevice));
+  if (pool) {
+    // the files merged in order into an empty accumulator, RT4_LIGHT_MERGE_MAX of them per call
+    std::vector<rt4_light_px> merged(static_cast<size_t>(cw[0]) * ch[0]);
+    std::memset(merged.data(), 0, light_bytes0);
+    const int64_t plane = static_cast<int64_t>(cw[0]) * ch[0];
+    for (size_t s0 = 0; s0 < light_pool.size(); s0 += RT4_LIGHT_MERGE_MAX)
+      RT4_CHECK(rt4_light_merge_host(ctx, merged.data(), cw[0], light_start.data() + s0 * static_cast<size_t>(plane), cw[0], plane,
+                                     static_cast<int32_t>(std::min<size_t>(RT4_LIGHT_MERGE_MAX, light_pool.size() - s0)), cw[0],
+                                     ch[0], err, sizeof err));
+    HIP_CHECK(hipMemcpy(d_light[0], merged.data(), light_bytes0, hipMemcpyHostToDevice));
+    RT4_CHECK(rt4_light_resolve_device(ctx, d_light[0], cw[0], base[0].light_to_color_conversion_coefficient, d_frame[0], format,
+                                       cw[0], cw[0], ch[0], nullptr, err, sizeof err));
+  }
+  // the last progressive frame number folded into the light accumulator: what --light-checkpoint records
+  int64_t light_issued = pool ? pool_issued : frames_done + frames;
+  double shards_ms = -1.0;  // --light-gpus: the slowest rank's time, in place of the events' below
+  unsigned long long shards_count = 0;
   HIP_CHECK(hipEventRecord(e0, nullptr));
   if (light && frames >= 1) {
     // every section's frames in one rt4_render_light_device call (frame n of every section has the same seed, as in
@@ -590,13 +818,24 @@ int main(int argc, char** argv) {
     for (int q = 0; q < n_img; q++) {
       std::vector<rt4_uniforms> lus(static_cast<size_t>(frames));
       cam.frame_number = frame_number;
-      for (int n = 1; n <= frames; n++)
+      for (int n = 1; n <= frames; n++)  // frames_done: the frames a --light-resume checkpoint already holds
         RT4_CHECK(rt4_camera_frame_uniforms(&cam, &base[q], sections[q],
-                                            static_cast<int32_t>(seed ^ (static_cast<uint32_t>(n) * 0x9E3779B9u)),
+                                            static_cast<int32_t>(seed ^ (static_cast<uint32_t>(frames_done + n) * 0x9E3779B9u)),
                                             &lus[static_cast<size_t>(n - 1)]));
       last_u[q] = lus.back();
       const rt4_region reg{0, 0, cw[q], ch[q], 0, 0};
-      if (adaptive) {
+      if (light_gpus > 0) {
+        // the accumulator of the section from light_gpus devices; resolve and everything after it run here, on the root's
+        // accumulator, as in a one-GPU run
+        const char* fail_env = std::getenv("RT4_RENDER_FAIL_RANK");  // the test hooks of --gpus
+        const char* stage_env = std::getenv("RT4_RENDER_FAIL_STAGE");
+        const std::vector<unsigned char> acc =
+            render_light_shards(light_gpus, light_split == "bands", band, scene, lus, cw[q], ch[q], rehearse,
+                                fail_env ? std::atoi(fail_env) : -1, stage_env && std::strcmp(stage_env, "gather") == 0,
+                                &shards_count, &shards_ms);
+        HIP_CHECK(hipSetDevice(device));  // the rank threads chose their own
+        HIP_CHECK(hipMemcpy(d_light[q], acc.data(), acc.size(), hipMemcpyHostToDevice));
+      } else if (adaptive) {
         // The loop of DESIGN.md §4.39 (Tracer.render_light_adaptive is the same loop): warm-up whole frames, then passes
         // of the selected tiles, every ad_full_every-th pass and a pass with an empty selection a whole frame; frame g is
         // rt4_progressive_uniforms(the section's uniforms with --seed, g), g running on across the passes.
@@ -648,6 +887,7 @@ int main(int argc, char** argv) {
           spent += n * listed;
           std::printf("adaptive %s: %s tiles %lld frames %d\n", names[q], kind, listed, n);
         }
+        light_issued = g;  // the loop's last frame number, whatever share of the image each frame covered
         HIP_CHECK(hipDeviceSynchronize());
         (void)hipFree(d_tiles);
         (void)hipFree(d_n);
@@ -688,6 +928,10 @@ int main(int argc, char** argv) {
   HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
   unsigned long long count = 0;
   HIP_CHECK(hipMemcpy(&count, d_count, sizeof count, hipMemcpyDeviceToHost));
+  if (shards_ms >= 0.0) {  // --light-gpus: the ranks counted and timed the frames
+    ms = static_cast<float>(shards_ms);
+    count += shards_count;
+  }
 
   for (int q = 0; q < n_img; q++) {
     std::vector<unsigned char> host(static_cast<size_t>(cw[q]) * ch[q] * px);
@@ -767,6 +1011,19 @@ int main(int argc, char** argv) {
     if (light) {
       // the error estimate of the section: its statistics and, with --noise-map, the display error q as grey
       const size_t npx = static_cast<size_t>(cw[q]) * ch[q];
+      if (raw || (q == 0 && !light_checkpoint_path.empty())) {
+        // --raw: the accumulator's bytes too; --light-checkpoint: the accumulator with what a resume or a pool must know
+        std::vector<unsigned char> acc(npx * sizeof(rt4_light_px));
+        HIP_CHECK(hipMemcpy(acc.data(), d_light[q], acc.size(), hipMemcpyDeviceToHost));
+        if (raw) write_raw(out + "_" + names[q] + "_light.raw", acc);
+        if (q == 0 && !light_checkpoint_path.empty()) {
+          RT4_CHECK(rt4_light_save(light_checkpoint_path.c_str(), reinterpret_cast<const rt4_light_px*>(acc.data()), cw[0], ch[0],
+                                   cw[0], light_issued, pool ? pool_seed : seed, pool ? pool_key : run_key,
+                                   pool ? RT4_LIGHT_POOLED : 0u, err, sizeof err));
+          std::printf("light checkpoint %s (frames issued %lld%s)\n", light_checkpoint_path.c_str(),
+                      static_cast<long long>(light_issued), pool ? ", pooled" : "");
+        }
+      }
       float* d_q = nullptr;
       rt4_noise_stats* d_stats = nullptr;
       if (noise_map) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_q), npx * sizeof(float)));
@@ -823,8 +1080,14 @@ int main(int argc, char** argv) {
       std::printf("checkpoint %s (%lld frames)\n", checkpoint_path.c_str(), static_cast<long long>(cam.frame_number) - 1);
     }
   }
-  std::printf("frames %d, images %d, intersections %llu, %.3f ms/frame, %.3e intersections/s\n", frames, n_img,
-              count, ms / frames, static_cast<double>(count) / (ms * 1e-3));
+  if (pool)
+    std::printf("pooled %zu light checkpoints, images 1\n", light_pool.size());
+  else if (light_gpus > 0)
+    std::printf("light gpus %d (%s), frames %d, images 1, intersections %llu, %.3f ms/frame, %.3e intersections/s\n", light_gpus,
+                light_split.c_str(), frames, count, ms / frames, static_cast<double>(count) / (ms * 1e-3));
+  else
+    std::printf("frames %d, images %d, intersections %llu, %.3f ms/frame, %.3e intersections/s\n", frames, n_img,
+                count, ms / frames, static_cast<double>(count) / (ms * 1e-3));
 
   for (int q = 0; q < n_img; q++) rt4_temporal_destroy(temporal[q]);
   for (int q = 0; q < n_img; q++)

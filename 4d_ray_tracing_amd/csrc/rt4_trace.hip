@@ -2954,6 +2954,7 @@ int rt4_debug_final_light(rt4_context* ctx, const float* drct, float* out, int64
 #include "rt4_light.h"
 #include "rt4_light_denoise.h"
 #include "rt4_light_tiles.h"
+#include "rt4_light_merge.h"
 
 extern "C" {
 

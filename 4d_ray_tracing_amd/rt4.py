@@ -189,6 +189,8 @@ class TileSelectParams(Structure):  # rt4.h rt4_tile_select_params
 
 
 SELECT_MAX_DILATE = 2  # rt4.h RT4_SELECT_MAX_DILATE
+LIGHT_MERGE_MAX = 16  # rt4.h RT4_LIGHT_MERGE_MAX
+LIGHT_POOLED = 0x1  # rt4.h RT4_LIGHT_POOLED: a light checkpoint of several seeds, not resumable
 
 
 def _gbuffer_dtype():
@@ -358,6 +360,18 @@ def _load(path=None):
         "rt4_render_light_tiles_host": ([c_void_p, POINTER(Uniforms), c_int32, POINTER(Region), c_void_p, c_int32, c_void_p,
                                          c_int64, POINTER(c_uint64)] + E, c_int),
         "rt4_context_select_bytes": ([c_void_p], c_uint64),
+        "rt4_light_merge_device": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
+                                    c_void_p] + E, c_int),
+        "rt4_light_merge_host": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32] + E,
+                                 c_int),
+        "rt4_light_bands_unpermute_device": ([c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p] + E,
+                                             c_int),
+        "rt4_frame_split": ([c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)] + E, c_int),
+        "rt4_light_save": ([c_char_p, c_void_p, c_int32, c_int32, c_int64, c_int64, c_uint32, c_uint32, c_uint32] + E, c_int),
+        "rt4_light_info": ([c_char_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), POINTER(c_uint32),
+                            POINTER(c_uint32), POINTER(c_uint32)] + E, c_int),
+        "rt4_light_load": ([c_char_p, c_void_p, c_int32, c_int32, c_int64, POINTER(c_int64), POINTER(c_uint32),
+                            POINTER(c_uint32), POINTER(c_uint32)] + E, c_int),
     }
     tolerant = os.environ.get("RT4_AB_TOLERANT") == "1"  # tools/abtest.sh: older builds lack newer exports
     for name, (argtypes, restype) in sig.items():
@@ -401,7 +415,9 @@ EXPORTED = (
     "rt4_light_noise_device rt4_light_noise_host "
     "rt4_light_denoise_params_default rt4_light_denoise_device rt4_light_denoise_host rt4_context_light_denoise_bytes "
     "rt4_tile_select_params_default rt4_light_select_tiles_device rt4_light_select_tiles_host "
-    "rt4_render_light_tiles_device rt4_render_light_tiles_host rt4_context_select_bytes"
+    "rt4_render_light_tiles_device rt4_render_light_tiles_host rt4_context_select_bytes "
+    "rt4_light_merge_device rt4_light_merge_host rt4_light_bands_unpermute_device rt4_frame_split "
+    "rt4_light_save rt4_light_info rt4_light_load"
 ).split()
 
 if ctypes.sizeof(SceneDesc) != lib.rt4_scene_desc_size() or ctypes.sizeof(Uniforms) != lib.rt4_uniforms_size():
@@ -774,6 +790,63 @@ def accum_load(path: str):
     _check(lib.rt4_accum_load(os.fsencode(path), c_void_p(frame.ctypes.data), info["format"], info["w"], info["h"],
                               info["w"], byref(n), byref(sd), err, len(err)), err)
     return frame, n.value, sd.value
+
+
+def light_bands_unpermute_device(gathered_ptr: int, image_ptr: int, width: int, height: int, world: int, rows_max: int,
+                                 band: int = 8, stream: int = 0) -> None:
+    """The light accumulator from world x rows_max gathered shard rows of rt4_light_px on the device
+    (rt4_light_bands_unpermute_device)."""
+    err = _errbuf()
+    _check(lib.rt4_light_bands_unpermute_device(c_void_p(gathered_ptr or None), c_void_p(image_ptr or None), width, height,
+                                                world, band, rows_max, c_void_p(stream or None), err, len(err)), err)
+
+
+def frame_split(n_frames: int, world: int, rank: int):
+    """(first, count) of the C ABI's frame split (rt4_frame_split; shard.py frame_split): `rank` renders the progressive
+    frames first + 1 .. first + count."""
+    first, count = c_int32(), c_int32()
+    err = _errbuf()
+    _check(lib.rt4_frame_split(n_frames, world, rank, byref(first), byref(count), err, len(err)), err)
+    return first.value, count.value
+
+
+def light_save(path: str, light, frames_issued: int, seed: int, key: int = 0, flags: int = 0, w: int | None = None) -> None:
+    """Checkpoint of a host light accumulator (h, stride) of LIGHT_DTYPE (rt4_light_save): frames_issued is the last
+    progressive frame number folded in, seed the base seed, key the run's accum_key (0 = not recorded), flags
+    LIGHT_POOLED for a pool of several seeds; w: the image width when rows are padded."""
+    assert light.dtype == LIGHT_DTYPE and light.flags["C_CONTIGUOUS"]
+    h = light.shape[0]
+    w = light.shape[1] if w is None else w
+    err = _errbuf()
+    _check(lib.rt4_light_save(os.fsencode(path), c_void_p(light.ctypes.data), w, h, light.shape[1], frames_issued,
+                              seed & 0xFFFFFFFF, key & 0xFFFFFFFF, flags & 0xFFFFFFFF, err, len(err)), err)
+
+
+def light_info(path: str) -> dict:
+    """The light checkpoint's header (rt4_light_info): w, h, frames_issued, seed, key, flags."""
+    w, h, n, sd, k, fl = c_int32(), c_int32(), c_int64(), c_uint32(), c_uint32(), c_uint32()
+    err = _errbuf()
+    _check(lib.rt4_light_info(os.fsencode(path), byref(w), byref(h), byref(n), byref(sd), byref(k), byref(fl), err,
+                              len(err)), err)
+    return {"w": w.value, "h": h.value, "frames_issued": n.value, "seed": sd.value, "key": k.value, "flags": fl.value}
+
+
+def light_load(path: str, light=None, w: int | None = None):
+    """(light, info) from a light checkpoint (rt4_light_load): light is an (h, w) array of LIGHT_DTYPE, or the array
+    given ((h, stride >= w), w: the image width when rows are padded); info as light_info."""
+    import numpy as np
+
+    if light is None:
+        info = light_info(path)
+        light = np.zeros((info["h"], info["w"]), LIGHT_DTYPE)
+    assert light.dtype == LIGHT_DTYPE and light.flags["C_CONTIGUOUS"]
+    h = light.shape[0]
+    w = light.shape[1] if w is None else w
+    n, sd, k, fl = c_int64(), c_uint32(), c_uint32(), c_uint32()
+    err = _errbuf()
+    _check(lib.rt4_light_load(os.fsencode(path), c_void_p(light.ctypes.data), w, h, light.shape[1], byref(n), byref(sd),
+                              byref(k), byref(fl), err, len(err)), err)
+    return light, {"w": w, "h": h, "frames_issued": n.value, "seed": sd.value, "key": k.value, "flags": fl.value}
 
 
 def write_png(path: str, frame, fmt: int | None = None) -> None:
@@ -1158,6 +1231,33 @@ class Tracer:
             len(err)), err)
         return se, q, tiles, {"pixels": st.pixels, "measured": st.measured, "above": st.above, "max_q": st.max_q,
                               "max_se": st.max_se}
+
+    def light_merge_device(self, dst_ptr: int, dst_stride: int, srcs_ptr: int, src_stride: int, src_plane_stride: int,
+                           n_srcs: int, w: int, h: int, stream: int = 0) -> None:
+        """Asynchronous: n_srcs device light accumulators (source s, pixel (i, j) at s * src_plane_stride + i * src_stride
+        + j pixels) merged in order into the one at dst_ptr (rt4_light_merge_device)."""
+        err = _errbuf()
+        _check(self._lib.rt4_light_merge_device(self._h, c_void_p(dst_ptr or None), dst_stride, c_void_p(srcs_ptr or None),
+                                                src_stride, src_plane_stride, n_srcs, w, h, c_void_p(stream or None), err,
+                                                len(err)), err)
+
+    def light_merge_host(self, dst, srcs, w: int | None = None):
+        """Synchronous: the host accumulators srcs (K, rows >= h, stride) of LIGHT_DTYPE (or a list of K equal 2-D arrays)
+        merged in order into dst (h, stride) in place; w: the image width when rows are padded. Rows of a source past
+        h pad its plane, as the rows past a rank's own do in a gather. Returns dst."""
+        import numpy as np
+
+        if isinstance(srcs, (list, tuple)):
+            srcs = np.stack(srcs)
+        assert dst.dtype == LIGHT_DTYPE and dst.flags["C_CONTIGUOUS"] and dst.ndim == 2
+        assert srcs.dtype == LIGHT_DTYPE and srcs.flags["C_CONTIGUOUS"] and srcs.ndim == 3
+        h = dst.shape[0]
+        w = dst.shape[1] if w is None else w
+        err = _errbuf()
+        _check(self._lib.rt4_light_merge_host(self._h, c_void_p(dst.ctypes.data), dst.shape[1], c_void_p(srcs.ctypes.data),
+                                              srcs.shape[2], srcs.shape[1] * srcs.shape[2], srcs.shape[0], w, h, err,
+                                              len(err)), err)
+        return dst
 
     def light_denoise_device(self, light_ptr: int, light_stride: int, gbuf_ptr: int, gbuf_stride: int, k: float,
                              frame_ptr: int, fmt: int, frame_stride: int, w: int, h: int,

@@ -87,6 +87,17 @@ def weak_plan(width: int, *, rows_per_rank: int, world: int, band: int = 8) -> B
     return make_plan(width, height=rows_per_rank * world, world=world, band=band)
 
 
+def frame_split(n_frames: int, world: int, rank: int) -> tuple[int, int]:
+    """(first, count) of `rank` when n_frames frames are split over `world` ranks in contiguous blocks (rt4_frame_split
+    is the same arithmetic): the rank renders the progressive frames first + 1 .. first + count into a whole-image light
+    accumulator, and the root merges the ranks' accumulators (rt4_light_merge_device). count is 0 when world exceeds
+    n_frames: an empty accumulator, which the merge ignores."""
+    if n_frames < 0 or world < 1 or not 0 <= rank < world:
+        raise ValueError("n_frames must be >= 0, world >= 1 and rank in [0, world)")
+    q, r = divmod(n_frames, world)
+    return rank * q + min(rank, r), q + (1 if rank < r else 0)
+
+
 def unpermute(gathered, plan: BandPlan):
     """(world, rows_max, W, C) gathered shards -> (height, W, C) image (torch or numpy): one row gather."""
     if plan.world == 1:

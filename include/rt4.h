@@ -925,6 +925,71 @@ int rt4_render_light_tiles_host(rt4_context* ctx, const rt4_uniforms* u, int32_t
 /* Bytes of the context's tile scratch: the selection's flags and the render's list copy (0 before the first call). */
 uint64_t rt4_context_select_bytes(const rt4_context* ctx);
 
+/* ---- light accumulators: merge, frame split, checkpoints (no reference counterpart) ----
+ * Two light accumulators of the same view that hold disjoint sets of frames combine into the accumulator of all
+ * their frames: Chan's pairwise update of the mean and the second moment. With it a render splits its frame numbers
+ * over GPUs (every rank renders the whole image for its block of frames, the root merges), a checkpoint resumes, and
+ * checkpoints of runs with other seeds pool.
+ * Definition (fp32 round-to-nearest, no contraction, division correctly rounded, fma explicit; the kernel matches it
+ * bit for bit; a NaN's payload is not defined; n >= 0 on both sides). State a (dst) and b (a source), per pixel:
+ *   b.n == 0: a keeps the bits of its mean, mean_y, m2 and n.  Otherwise a.n == 0: a takes b's.  Otherwise:
+ *   N = (int64)a.n + b.n; fb = (float)b.n / (float)N; wa = (float)a.n * fb;
+ *   mean_c' = fma(b.mean_c - a.mean_c, fb, a.mean_c);
+ *   dy = b.mean_y - a.mean_y; mean_y' = fma(dy, fb, a.mean_y);
+ *   m2' = fma(dy * dy, wa, a.m2 + b.m2) (the product, the sum, then one fma);  n' = min(N, INT32_MAX).
+ * reserved is written as 0 in all three cases. Empty operands are exact identities in either order, and m2 stays
+ * >= 0 for m2 >= 0. Merging an accumulator of ONE frame into a gives the mean and mean_y of folding that frame
+ * (rt4_render_light_device) bit for bit while N < INT32_MAX: fb is then 1 / (float)N, the fold's inv. It does NOT give
+ * the fold's m2, which is fma(dy, y - mean_y', m2): the same number rounded differently. A merge of blocks is
+ * therefore as accurate as one sequential fold (relative error against float64 within 1.25x of the
+ * fold's), not bit-equal to it.
+ * Source s, pixel (i, j) is d_srcs[s * src_plane_stride + i * src_stride + j]: the rank-major layout a gather leaves
+ * on the root. The sources are applied as the left fold dst = merge(dst, src_0), then src_1, ...: one call with
+ * n_srcs sources equals n_srcs calls with one source each bit for bit, and moves 32 (n_srcs + 2) B per pixel where
+ * those move 96 n_srcs. RT4_ERR_ARG, nothing written, for a NULL pointer, n_srcs outside [1, RT4_LIGHT_MERGE_MAX],
+ * w or h outside [1, 65535], a row stride below w, a plane stride below the span of one source image
+ * ((h - 1) * src_stride + w; also with one source), a pointer not aligned to 16 B, or a dst that overlaps any source. Asynchronous on
+ * `stream`, no allocation, no synchronisation. Ordered with the context's other launches. */
+#define RT4_LIGHT_MERGE_MAX 16
+int rt4_light_merge_device(rt4_context* ctx, rt4_light_px* d_dst, int64_t dst_stride, const rt4_light_px* d_srcs,
+                           int64_t src_stride, int64_t src_plane_stride, int32_t n_srcs, int32_t w, int32_t h, void* stream,
+                           char* err, size_t errlen);
+/* The same on host accumulators (synchronous; the padding of dst keeps its bytes). */
+int rt4_light_merge_host(rt4_context* ctx, rt4_light_px* dst, int64_t dst_stride, const rt4_light_px* srcs,
+                         int64_t src_stride, int64_t src_plane_stride, int32_t n_srcs, int32_t w, int32_t h, char* err,
+                         size_t errlen);
+/* rt4_bands_unpermute_device for light accumulators: d_gathered holds world x rows_max rows of width rt4_light_px,
+ * rank-major, d_image receives height rows of width pixels (row stride width). The same kernel in 16-B words and the
+ * same checks; both pointers 16-byte aligned (RT4_ERR_ARG otherwise). Asynchronous on stream. */
+int rt4_light_bands_unpermute_device(const rt4_light_px* d_gathered, rt4_light_px* d_image, int32_t width, int32_t height,
+                                     int32_t world, int32_t band, int32_t rows_max, void* stream, char* err, size_t errlen);
+/* The block of `rank` when n_frames frames are split over `world` ranks in contiguous blocks: count = n_frames / world
+ * + (rank < n_frames % world), first = the frames of the ranks before it. The rank renders frames first + 1 ..
+ * first + count of rt4_progressive_uniforms; with count == 0 it contributes an empty accumulator, which the merge
+ * ignores (4d_ray_tracing_amd/shard.py frame_split is the same arithmetic). RT4_ERR_ARG for a NULL pointer,
+ * n_frames < 0, world < 1 or rank outside [0, world). */
+int rt4_frame_split(int32_t n_frames, int32_t world, int32_t rank, int32_t* first, int32_t* count, char* err,
+                    size_t errlen);
+/* Checkpoint of a light accumulator. File (little-endian): "RT4LIT1\0", int32 version (1), w, h, int64 frames_issued,
+ * uint32 seed, uint32 key (rt4_accum_key of the run, 0 = not recorded), uint32 flags, uint32 0, then h rows of w
+ * rt4_light_px, rows top first, no padding. frames_issued is the last frame number of rt4_progressive_uniforms that
+ * was folded in: a resumed run continues with frames_issued + 1. It is a property of the run, not of any pixel: after
+ * an adaptive run the pixels' n differ from it and from each other. RT4_LIGHT_POOLED marks a file that holds runs of
+ * several seeds (seed and frames_issued are then those of the first run pooled) and cannot be resumed. A save writes
+ * <path>.tmp, flushes it to the disk and renames it over path, as rt4_accum_save does. */
+#define RT4_LIGHT_FILE_VERSION 1
+#define RT4_LIGHT_POOLED 0x1u
+int rt4_light_save(const char* path, const rt4_light_px* light, int32_t w, int32_t h, int64_t row_stride_px,
+                   int64_t frames_issued, uint32_t seed, uint32_t key, uint32_t flags, char* err, size_t errlen);
+/* Header only: any output pointer may be null. RT4_ERR_PARSE for a file that is not a light checkpoint (wrong magic or
+ * version, a bad header) or whose size is not the header's plus w * h pixels. */
+int rt4_light_info(const char* path, int32_t* w, int32_t* h, int64_t* frames_issued, uint32_t* seed, uint32_t* key,
+                   uint32_t* flags, char* err, size_t errlen);
+/* Reads the pixels into a host accumulator of the checkpoint's w and h (RT4_ERR_ARG if the caller's differ; bytes
+ * outside the image keep their values); the header fields as rt4_light_info. Nothing is written for a file that is refused. */
+int rt4_light_load(const char* path, rt4_light_px* light, int32_t w, int32_t h, int64_t row_stride_px,
+                   int64_t* frames_issued, uint32_t* seed, uint32_t* key, uint32_t* flags, char* err, size_t errlen);
+
 /* ---- diagnostics (used by the parity tests; not on the render path) ------------------------- */
 /* Bytes of the context's frame-colour scratch for pipelined frames (0 before any pipelined launch or
  * reservation; a scene that runs frame by frame never allocates it). */
