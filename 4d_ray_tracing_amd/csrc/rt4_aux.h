@@ -92,7 +92,10 @@ constexpr float CYL_PRECULL_K = 8e-6f;
 // i.e. a ray starting on (within ~5e-4 r of) one of the infinite cylinders, anywhere; the NaN then
 // passes the filters (the reference's comparisons are false on NaN). So the skip also requires the
 // origin's squared distance to each axes plane to stay out of [0.99 r^2, 1.01 r^2] for the radii of
-// that plane's cylinders (band[]). Then the skipped test's result is exactly "no hit".
+// that plane's cylinders (band[]), each band widened by 8e-6 |p - c|^2: the kernel's two distances come from the
+// coordinates along plane A's axes, which are orthonormal only to the 1e-6 checked below, and from fp32 dots, so
+// their error grows with |p - c|^2 and not with r^2 (rt4_fast.h far_from). Then the skipped test's result is
+// exactly "no hit".
 // r2m = +inf disables (non-orthonormal axes, different points).
 struct alignas(64) BoundBall {
   float center[4];

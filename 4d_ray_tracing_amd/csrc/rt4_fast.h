@@ -388,8 +388,14 @@ __device__ __forceinline__ bool cell_hit(const float4* cell, const Ray& ray, flo
 // (h < 0 || cos_dn < 0, the far-face skip) for all lanes, then each lane's remaining candidate cells
 // in cell order until the first hit, read from LDS. Same first-hit-in-order result; a wave pays for
 // max-over-lanes(candidates tried) exact tests instead of all 8 cells.
+// PROBE (rt4_debug_bound_skip only): also writes the cull pass's decision to *probe, bit 2 = far, bits 8-15 = the
+// rejected cells. A compile-time branch of this function, not a helper the cull pass is moved into: with the pass
+// in a function of its own (far by reference, or packed into the result) every hypercube kernel came out with
+// other registers (tools/kernel_diff.py), and a copy in the probe could drift from the kernels.
+template <bool PROBE = false>
 __device__ __forceinline__ Cand hypercube_cand(const rt4_scene_desc* __restrict__ S, const SceneAux* __restrict__ X,
-                                               const float4* cells, int i, uint32_t base, const Ray& ray) {
+                                               const float4* cells, int i, uint32_t base, const Ray& ray,
+                                               uint32_t* probe = nullptr) {
   const rt4_hypercube& hc = S->hypercubes[i];
   float l2 = 0.0f;
   bool far = false;
@@ -435,6 +441,7 @@ __device__ __forceinline__ Cand hypercube_cand(const rt4_scene_desc* __restrict_
       cand |= rejected ? 0u : (1u << k);
     }
   }
+  if constexpr (PROBE) *probe = (far ? 4u : 0u) | ((~cand & 0xFFu) << 8);
   Cand res = no_cand();
   while (cand) {
 #ifdef RT4_LANESTATS  // diagnostic: pending-cell trips and their active lanes (counter[58], [59])
@@ -491,6 +498,7 @@ __device__ __forceinline__ void for_count(int runtime_n, F&& body) {
 // hits of origins near a cylinder keep the exact path through the same band check. So the skip is exact too.
 // (r06-v53: config 5 +1.5 %; r06-v54, in every kernel with the behind test as max(b, 0) inside the line test, which
 // fits the mirror room's registers: config 4 +3.1 %)
+constexpr float BAND_SLACK = 8e-6f;
 __device__ __forceinline__ bool far_from(const BoundBall& bb, const Ray& ray) {
   const f16v k = *reinterpret_cast<const f16v*>(&bb);  // centre, a1, a2, r2m, band[0..2]
   const f16v m = *(reinterpret_cast<const f16v*>(&bb) + 1);  // band[3..7]
@@ -498,8 +506,14 @@ __device__ __forceinline__ bool far_from(const BoundBall& bb, const Ray& ray) {
   const float a = dot(pc, pc), b = dot(pc, ray.drct), l2 = dot(ray.drct, ray.drct);
   const float u1 = dot(pc, V4{k[4], k[5], k[6], k[7]}), u2 = dot(pc, V4{k[8], k[9], k[10], k[11]});
   const float dB = fmaf_(u1, u1, u2 * u2), dA = a - dB;  // squared distances to plane B and plane A
-  const bool near_surface = (dA >= k[13] && dA <= k[14]) || (dA >= k[15] && dA <= m[0]) ||
-                            (dB >= m[1] && dB <= m[2]) || (dB >= m[3] && dB <= m[4]);
+  // Both carry an error that grows with a, not with r^2: the axes are orthonormal only to the host's 1e-6 (up to
+  // 4e-6 a between these coordinates and the distances the exact test projects out) and the dots round (~1e-6 a).
+  // Far out along an axes plane that exceeds the band's 1 % of r^2, and the NaN hit of an origin on a cylinder was
+  // skipped (tests/test_bound_ball_ref.py found it on the oracle alone). So each band is widened by BAND_SLACK a.
+  const float sl = BAND_SLACK * a;
+  const float dAl = dA - sl, dAh = dA + sl, dBl = dB - sl, dBh = dB + sl;
+  const bool near_surface = (dAh >= k[13] && dAl <= k[14]) || (dAh >= k[15] && dAl <= m[0]) ||
+                            (dBh >= m[1] && dBl <= m[2]) || (dBh >= m[3] && dBl <= m[4]);
   // both skips as one v_max: with b clamped at 0 the line test reads a (1 - 4e-6) > R2m when b <= 0, i.e. the origin
   // outside the inflated ball (a finite b: a, l2 < 1e30)
   const float bp = fmaxf(b, 0.0f);

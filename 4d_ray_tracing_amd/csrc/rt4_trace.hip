@@ -1411,6 +1411,25 @@ __global__ void rt4_final_light_kernel(const rt4_scene_desc* __restrict__ S, con
   o[0] = fl.x; o[1] = fl.y; o[2] = fl.z;
 }
 
+// The bounding-ball decisions of n rays, one lane each (rt4_debug_bound_skip, rt4.h for the bits): far_from and
+// hypercube_cand's cull pass as the trace kernels call them, on the context's scene and aux block. rays: n x 8 floats.
+__global__ void rt4_bound_skip_kernel(const rt4_scene_desc* __restrict__ S, const SceneAux* __restrict__ X,
+                                      const float* __restrict__ rays, uint32_t* __restrict__ out, int64_t n) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const float* r = rays + 8 * t;
+  const Ray ray{ld4(r), ld4(r + 4)};
+  uint32_t m = 0;
+  if (S->n_unions > 0 && RT4_BOUND_SKIP && far_from(X->union_bound[0], ray)) m |= 1u;
+  if (S->n_tigers > 0 && RT4_BOUND_SKIP && far_from(X->tiger_bound[0], ray)) m |= 2u;
+  if (S->n_hypercubes > 0) {  // the cells from the aux block itself, as rt4_find_kernel reads them
+    uint32_t cull = 0;
+    (void)hypercube_cand<true>(S, X, reinterpret_cast<const float4*>(X->prims) - HYPER_CELLS_LDS, 0, 0u, ray, &cull);
+    m |= cull;
+  }
+  out[t] = m;
+}
+
 // Tile order for the pixel queue (longest work first): one thread per 8x8 tile traces the primary ray
 // of the tile's centre pixel; tiles whose ray hits something go to the front of `order`, sky tiles to
 // the back. The queue hands tiles out in this order, so the slow tiles do not form the drain at the
@@ -2938,6 +2957,32 @@ int rt4_debug_final_light(rt4_context* ctx, const float* drct, float* out, int64
   if (dout) (void)hipFree(dout);
   if (e != hipSuccess) {
     rt4_set_err(err, errlen, "debug_final_light failed: %s", hipGetErrorString(e));
+    return RT4_ERR_HIP;
+  }
+  return RT4_OK;
+}
+
+int rt4_debug_bound_skip(rt4_context* ctx, const float* rays, uint32_t* out_mask, int64_t n, char* err, size_t errlen) {
+  if (!ctx || !rays || !out_mask || n < 0) return rt4_set_err(err, errlen, "bad argument"), RT4_ERR_ARG;
+  if (!ctx->has_scene) return rt4_set_err(err, errlen, "context has no scene"), RT4_ERR_ARG;
+  if (n == 0) return RT4_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  float* dr = nullptr;
+  uint32_t* dout = nullptr;
+  HIP_TRY(hipMalloc(&dr, n * 8 * sizeof(float)));
+  hipError_t e = hipMalloc(&dout, n * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemcpy(dr, rays, n * 8 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(rt4_bound_skip_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, 0, ctx->d_scene,
+                       scene_aux(ctx), dr, dout, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out_mask, dout, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  (void)hipFree(dr);
+  if (dout) (void)hipFree(dout);
+  if (e != hipSuccess) {
+    rt4_set_err(err, errlen, "debug_bound_skip failed: %s", hipGetErrorString(e));
     return RT4_ERR_HIP;
   }
   return RT4_OK;

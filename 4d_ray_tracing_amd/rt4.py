@@ -249,6 +249,7 @@ def _load(path=None):
         "rt4_debug_eval": ([c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
         "rt4_debug_find_intersection": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
         "rt4_debug_final_light": ([c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
+        "rt4_debug_bound_skip": ([c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
         "rt4_context_kernel_shape": ([c_void_p], c_uint32),
         "rt4_debug_verify_sqrt": ([c_void_p, POINTER(c_uint64)] + E, c_int),
         "rt4_frame_format_bytes": ([c_int32], c_int32),
@@ -404,7 +405,7 @@ EXPORTED = (
     "rt4_accum_save_key rt4_accum_key rt4_accum_key_of "
     "rt4_scene_surface_count rt4_scene_surface rt4_render_gbuffer_device rt4_render_gbuffer_host "
     "rt4_denoise_params_default rt4_denoise_device rt4_denoise_host rt4_context_denoise_bytes "
-    "rt4_debug_final_light "
+    "rt4_debug_final_light rt4_debug_bound_skip "
     "rt4_reproject_params_default rt4_reproject_device rt4_reproject_host rt4_temporal_blend_device rt4_temporal_create "
     "rt4_temporal_destroy rt4_temporal_reset rt4_temporal_frame_device rt4_temporal_image rt4_temporal_history "
     "rt4_temporal_gbuffer rt4_temporal_read_host rt4_temporal_bytes "
@@ -1488,6 +1489,18 @@ class Tracer:
         err = _errbuf()
         _check(self._lib.rt4_debug_final_light(self._h, c_void_p(drct.ctypes.data), c_void_p(out.ctypes.data),
                                                drct.shape[0], err, len(err)), err)
+        return out
+
+    def debug_bound_skip(self, rays):
+        """The trace kernels' bounding-ball decisions for rays (n, 8) (rt4_debug_bound_skip): (n,) uint32, bit 0 the
+        union's skip, bit 1 the tiger's, bit 2 the hypercube's far flag, bits 8-15 its rejected cells."""
+        import numpy as np
+
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        out = np.empty(rays.shape[0], np.uint32)
+        err = _errbuf()
+        _check(self._lib.rt4_debug_bound_skip(self._h, c_void_p(rays.ctypes.data), c_void_p(out.ctypes.data),
+                                              rays.shape[0], err, len(err)), err)
         return out
 
 

@@ -1025,6 +1025,17 @@ int rt4_debug_find_intersection(rt4_context* ctx, const float* rays, float* out,
  * Synchronous; host buffers. RT4_ERR_ARG (nothing written) for a NULL pointer, n < 0 or a context without a scene. */
 int rt4_debug_final_light(rt4_context* ctx, const float* drct, float* out, int64_t n, char* err, size_t errlen);
 
+/* The trace kernels' bounding-ball decisions (their own device functions, on the context's scene) for n rays, one
+ * lane each. rays: n x 8 floats (point xyzw, drct xyzw), as they are. out_mask: one uint32 per ray:
+ *   bit 0      the exact test of union 0 is skipped (the ray's line clears its ball, or the ball lies behind),
+ *   bit 1      the same for tiger 0,
+ *   bit 2      the ray's line clears hypercube 0's ball (its faces skip the exact test unless nearly parallel),
+ *   bits 8-15  the cells of hypercube 0 that the cull pass rejected (bit 8 + k: cell k).
+ * A figure that the scene lacks gives 0 in its bits; so does a ball the host disabled. The skips belong to the
+ * specialised kernels (the generic find_intersection tests everything); the mask is the same under either flag.
+ * Synchronous; host buffers. RT4_ERR_ARG (nothing written) for a NULL pointer, n < 0 or a context without a scene. */
+int rt4_debug_bound_skip(rt4_context* ctx, const float* rays, uint32_t* out_mask, int64_t n, char* err, size_t errlen);
+
 /* Counts the 32-bit patterns x for which the kernel's sqrt (fast path without input scaling) differs
  * from the IEEE square root; 0 expected. Exhaustive over all 2^32 inputs on the device (~10 ms). */
 int rt4_debug_verify_sqrt(rt4_context* ctx, uint64_t* mismatches, char* err, size_t errlen);
