@@ -1783,8 +1783,14 @@ const SceneAux* scene_aux(const rt4_context* c) {
 
 float fbits(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 
-// Largest x >= 0 with RN(sqrt(x)) <= r: then sqrt(x) > r  <=>  x > gt.
+// The band filters' thresholds (rt4_fast.h union_cand, tiger_pair, tiger_quarter): for every
+// q = dot(v, v), that is +0, a denormal, a normal, +inf or NaN,
+//   q > gt(r)  <=>  RN(sqrt(q)) > r      and      q < lt(r)  <=>  RN(sqrt(q)) < r.
+// gt: the largest x >= 0 with RN(sqrt(x)) <= r. No q is above a NaN or infinite r, +inf included, so gt = +inf; every
+// q >= +0 is above a negative r and NaN is not, so gt is negative there.
 float sqrt_gt_threshold(float r) {
+  if (std::isnan(r) || r == INFINITY) return INFINITY;
+  if (r < 0.0f) return -1.0f;
   uint32_t lo = 0, hi = 0x7F800000u;  // predicate true at lo (sqrt(0) = 0 <= r), false at +inf
   while (hi - lo > 1) {
     const uint32_t mid = lo + (hi - lo) / 2;
@@ -2985,6 +2991,13 @@ int rt4_debug_bound_skip(rt4_context* ctx, const float* rays, uint32_t* out_mask
     rt4_set_err(err, errlen, "debug_bound_skip failed: %s", hipGetErrorString(e));
     return RT4_ERR_HIP;
   }
+  return RT4_OK;
+}
+
+int rt4_debug_sqrt_thresholds(float r, float* gt, float* lt) {
+  if (!gt || !lt) return RT4_ERR_ARG;
+  *gt = sqrt_gt_threshold(r);
+  *lt = sqrt_lt_threshold(r);
   return RT4_OK;
 }
 

@@ -250,6 +250,7 @@ def _load(path=None):
         "rt4_debug_find_intersection": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
         "rt4_debug_final_light": ([c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
         "rt4_debug_bound_skip": ([c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
+        "rt4_debug_sqrt_thresholds": ([c_float, POINTER(c_float), POINTER(c_float)], c_int),
         "rt4_context_kernel_shape": ([c_void_p], c_uint32),
         "rt4_debug_verify_sqrt": ([c_void_p, POINTER(c_uint64)] + E, c_int),
         "rt4_frame_format_bytes": ([c_int32], c_int32),
@@ -405,7 +406,7 @@ EXPORTED = (
     "rt4_accum_save_key rt4_accum_key rt4_accum_key_of "
     "rt4_scene_surface_count rt4_scene_surface rt4_render_gbuffer_device rt4_render_gbuffer_host "
     "rt4_denoise_params_default rt4_denoise_device rt4_denoise_host rt4_context_denoise_bytes "
-    "rt4_debug_final_light rt4_debug_bound_skip "
+    "rt4_debug_final_light rt4_debug_bound_skip rt4_debug_sqrt_thresholds "
     "rt4_reproject_params_default rt4_reproject_device rt4_reproject_host rt4_temporal_blend_device rt4_temporal_create "
     "rt4_temporal_destroy rt4_temporal_reset rt4_temporal_frame_device rt4_temporal_image rt4_temporal_history "
     "rt4_temporal_gbuffer rt4_temporal_read_host rt4_temporal_bytes "
@@ -868,6 +869,15 @@ def frame_format_bytes(fmt: int) -> int:
 
 
 FRAME_NUMPY = {FRAME_RGBA32F: "float32", FRAME_RGBA16F: "float16", FRAME_RGBA8: "uint8"}
+
+
+def debug_sqrt_thresholds(r: float, library=None):
+    """(gt, lt) of rt4_debug_sqrt_thresholds: the band-filter thresholds set_scene makes from the radius r, as
+    Python floats holding float32 values. Host only: no context, no device."""
+    gt, lt = c_float(), c_float()
+    if (library or lib).rt4_debug_sqrt_thresholds(c_float(r), byref(gt), byref(lt)) != 0:
+        raise RT4Error(-1, "rt4_debug_sqrt_thresholds failed")
+    return gt.value, lt.value
 
 
 def progressive_uniforms(base: Uniforms, frame_number: int) -> Uniforms:

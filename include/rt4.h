@@ -1036,6 +1036,14 @@ int rt4_debug_final_light(rt4_context* ctx, const float* drct, float* out, int64
  * Synchronous; host buffers. RT4_ERR_ARG (nothing written) for a NULL pointer, n < 0 or a context without a scene. */
 int rt4_debug_bound_skip(rt4_context* ctx, const float* rays, uint32_t* out_mask, int64_t n, char* err, size_t errlen);
 
+/* The thresholds rt4_context_set_scene makes from a radius r for the band filters of the union and the tiger, which
+ * compare the squared distance q to the other axes pair without a square root: for every float q that dot(v, v) can
+ * give (+0, denormals, normals, +inf, NaN)
+ *   q > *gt  <=>  sqrt(q) > r      and      q < *lt  <=>  sqrt(q) < r      (sqrt correctly rounded).
+ * *gt is +inf for a NaN or infinite r and negative for a negative one; *lt is 0 for a NaN, zero or negative r.
+ * Host only: no context, no device. RT4_ERR_ARG for a NULL pointer. */
+int rt4_debug_sqrt_thresholds(float r, float* gt, float* lt);
+
 /* Counts the 32-bit patterns x for which the kernel's sqrt (fast path without input scaling) differs
  * from the IEEE square root; 0 expected. Exhaustive over all 2^32 inputs on the device (~10 ms). */
 int rt4_debug_verify_sqrt(rt4_context* ctx, uint64_t* mismatches, char* err, size_t errlen);

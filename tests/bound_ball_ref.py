@@ -46,8 +46,14 @@ def _next_up32(x):
 
 
 def sqrt_gt_threshold(r):
-    """The host's sqrt_gt_threshold: the largest float32 x >= 0 with RN(sqrt(x)) <= r (0 when there is none)."""
+    """The host's sqrt_gt_threshold: the largest float32 x >= 0 with RN(sqrt(x)) <= r; +inf for a NaN or infinite r
+    and -1 for a negative one (no q = dot(v, v) is above the former, every q is above the latter). The definition it
+    serves and its tests are band_filter_ref.gt and test_band_filter_ref.py."""
     r = F32(r)
+    if np.isnan(r) or r == F32(np.inf):
+        return float("inf")
+    if r < 0:
+        return -1.0
     lo, hi = 0, 0x7F800000
     while hi - lo > 1:
         mid = lo + (hi - lo) // 2
