@@ -195,7 +195,7 @@ int render_light(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, cons
   job.region = *region;
   job.d_frame = d_light;  // launch_jobs wants a frame; the fold takes the accumulator as an argument of its own
   job.row_stride_px = row_stride_px;
-  const LightTarget lt{d_light, row_stride_px};
+  const LightTarget lt{d_light, row_stride_px, tl};
   const int32_t chunk = rt4_context_frames_per_launch(ctx, region->w, region->h);
   int32_t seeds[RT4_MAX_FRAMES];
   float parts[RT4_MAX_FRAMES];
@@ -207,8 +207,8 @@ int render_light(rt4_context* ctx, const rt4_uniforms* u, int32_t n_frames, cons
       seeds[f] = u[f0 + f].seed;
       parts[f] = 1.0f;
     }
-    const FramePlan fp{n, seeds, parts};
-    const int st = launch_jobs(ctx, &job, 1, RT4_FRAME_RGBA32F, d_counter, stream, err, errlen, &fp, &lt, tl);
+    const FramePlan fp{n, seeds, parts, &lt};
+    const int st = launch_jobs(ctx, &job, 1, RT4_FRAME_RGBA32F, d_counter, stream, err, errlen, &fp);
     if (st != RT4_OK) return st;
   }
   return RT4_OK;

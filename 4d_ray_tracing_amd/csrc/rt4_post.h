@@ -1,8 +1,9 @@
-// rt4_post.h — what every post pass of rt4.h shares and none owns: the argument checks of strided
-// device images, the launch bracket that orders a pass with the context's launches, the 32x8 pixel grid, the stores and
-// decodes of the frame formats, the staging of the _host variants and the context's growing scratch buffers. Part of
-// rt4_trace.hip's translation unit, included ahead of the pass headers (rt4_denoise.h ... rt4_light_merge.h): it needs
-// the context, HIP_TRY and the blend_* store helpers from there and nothing from any pass.
+// rt4_post.h — what the render path and every post pass of rt4.h share and none owns: the
+// argument checks of strided device images, the launch bracket that orders a pass with the context's launches, the 32x8
+// pixel grid, the stores and decodes of the frame formats, the staging of the _host variants and the context's growing
+// scratch buffers. Part of rt4_trace.hip's translation unit, included directly behind the context and HIP_TRY, ahead of
+// the render entry points and the pass headers (rt4_denoise.h ... rt4_light_merge.h): it needs the context, HIP_TRY and
+// the blend_* store helpers from there and nothing from the launch path or any pass.
 #pragma once
 
 namespace {

@@ -1721,11 +1721,9 @@ struct rt4_context {
   uint32_t shape = GENERIC;
   WEntry* d_wlut = nullptr;
   unsigned* d_queue = nullptr;  // QUEUE_SLOTS words
-  unsigned* d_order = nullptr;  // tile order (rt4_tile_order_kernel) + 2 end counters
-  void* d_fcolor = nullptr;     // frame colours of pipelined launches (rt4_render_frames_device)
-  size_t fcolor_bytes = 0;
-  size_t order_cap = 0;         // tiles it holds
-  bool order_valid = false;     // d_order holds the order for order_args (same scene)
+  CtxScratch order;             // in 4-B words: the tile order (rt4_tile_order_kernel), then its 2 end counters
+  CtxScratch fcolor;            // in bytes: frame colours of pipelined launches (rt4_render_frames_device)
+  bool order_valid = false;     // order holds the order for order_args (same scene)
   KernelArgs order_args{};
   hipEvent_t done = nullptr;    // recorded after each launch: launches on another stream wait for it
   hipStream_t last_stream = nullptr;
@@ -1758,7 +1756,7 @@ struct rt4_context {
   CtxScratch light_denoise;  // in pixels
   // Scratch of adaptive light sampling (rt4_light_tiles.h): the per-tile flags of rt4_light_select_tiles_device, and the
   // clamped copy of a tile list that rt4_render_light_tiles_device hands the trace kernel (followed by the two words
-  // {0, 1} it reads as KernelArgs::order_ends). Apart from d_order: the pre-pass order stays valid across tile launches.
+  // {0, 1} it reads as KernelArgs::order_ends). Apart from order: the pre-pass order stays valid across tile launches.
   CtxScratch select;     // in 4-B words: one per tile
   CtxScratch tile_list;  // in 4-B words: one per tile and the two at the end
 };
@@ -1771,6 +1769,9 @@ struct rt4_context {
       return RT4_ERR_HIP;                                                                        \
     }                                                                                            \
   } while (0)
+
+// The layer the render path below and every post pass share.
+#include "rt4_post.h"
 
 namespace {
 
@@ -1838,6 +1839,20 @@ DivSweep div_sweep(float b, bool full) {
   return d;
 }
 
+// The sweep of rt4_sky_threshold_kernel for the angular size ang: every float, or, for ang <= 1 unless `full`, only
+// the c in (0.5, 1] that can have acos_(c) < ang.
+struct SkySweep {
+  uint32_t lo;
+  uint64_t count;
+  unsigned blocks;
+};
+SkySweep sky_sweep(float ang, bool full) {
+  if (full || !(ang <= 1.0f)) return SkySweep{0u, 1ull << 32, 65536u};
+  return SkySweep{0x3F000001u, 0x3F800000ull - 0x3F000001ull + 1ull, 512u};
+}
+// The float of the sweep's result, an order key (order_key of the kernel).
+float order_key_float(uint32_t key) { return fbits((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key); }
+
 // Verifies the divisors and the sky threshold not yet in the caches: one launch for all divisors, one
 // for the threshold, one copy back.
 int verify_constants(rt4_context* ctx, const std::vector<float>& divisors, bool need_sky, float ang, char* err,
@@ -1867,11 +1882,8 @@ int verify_constants(rt4_context* ctx, const std::vector<float>& divisors, bool 
     HIP_TRY(hipGetLastError());
   }
   if (sky) {
-    const bool small = ang <= 1.0f;  // only c in (0.5, 1] can have acos_(c) < ang (rt4_sky_threshold_kernel)
-    const uint32_t lo = small ? 0x3F000001u : 0u;
-    const uint64_t count = small ? (0x3F800000ull - 0x3F000001ull + 1ull) : (1ull << 32);
-    hipLaunchKernelGGL(rt4_sky_threshold_kernel, dim3(small ? 512 : 65536), dim3(256), 0, 0, ang, lo, count,
-                       ctx->d_scratch + n);
+    const SkySweep w = sky_sweep(ang, false);
+    hipLaunchKernelGGL(rt4_sky_threshold_kernel, dim3(w.blocks), dim3(256), 0, 0, ang, w.lo, w.count, ctx->d_scratch + n);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipMemcpy(res.data(), ctx->d_scratch, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -2054,14 +2066,8 @@ int build_aux(rt4_context* ctx, const rt4_scene_desc& s, SceneAux* a, char* err,
       std::lock_guard<std::mutex> lock(g_verify_mu);
       best = g_sky_best.at(fkey(s.sun.angular_size));
     }
-    if (best == 0xFFFFFFFFu) {
-      a->sky_c_star = INFINITY;  // acos never below the angular size: always sky
-    } else {
-      const uint32_t bits = (best & 0x80000000u) ? (best & 0x7FFFFFFFu) : ~best;
-      float m;
-      std::memcpy(&m, &bits, 4);
-      a->sky_c_star = std::nextafter(m, -INFINITY);
-    }
+    // no key: acos never below the angular size, always sky
+    a->sky_c_star = best == 0xFFFFFFFFu ? INFINITY : std::nextafter(order_key_float(best), -INFINITY);
   } else {
     a->sky_c_star = -INFINITY;
   }
@@ -2171,8 +2177,8 @@ int rt4_context_create(int device, uint32_t flags, rt4_context** out, char* err,
   if (e == hipSuccess) e = hipMalloc(&c->d_ocount, RT4_OVERLAP_SLOTS * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMemset(c->d_ocount, 0, RT4_OVERLAP_SLOTS * sizeof(unsigned long long));
   if (e == hipSuccess) {  // tile order for frames up to 2^18 tiles (16.7 M pixels); larger ones grow it once
-    e = hipMalloc(&c->d_order, ((size_t(1) << 18) + 2) * sizeof(unsigned));
-    if (e == hipSuccess) c->order_cap = size_t(1) << 18;
+    e = hipMalloc(&c->order.d, ((size_t(1) << 18) + 2) * sizeof(unsigned));
+    if (e == hipSuccess) c->order.cap = (size_t(1) << 18) + 2;
   }
   if (e == hipSuccess) {
     // The first host<->device copies of the process (the runtime sets up its staging buffers: ~7 ms,
@@ -2215,8 +2221,6 @@ void rt4_context_destroy(rt4_context* ctx) {
   if (ctx->d_scene) (void)hipFree(ctx->d_scene);
   if (ctx->d_wlut) (void)hipFree(ctx->d_wlut);
   if (ctx->d_queue) (void)hipFree(ctx->d_queue);
-  if (ctx->d_order) (void)hipFree(ctx->d_order);
-  if (ctx->d_fcolor) (void)hipFree(ctx->d_fcolor);
   if (ctx->done) (void)hipEventDestroy(ctx->done);
   for (int k = 0; k < RT4_OVERLAP_SLOTS; k++) {
     if (ctx->side[k]) {
@@ -2230,7 +2234,8 @@ void rt4_context_destroy(rt4_context* ctx) {
   if (ctx->d_ocount) (void)hipFree(ctx->d_ocount);
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
   if (ctx->d_eval) (void)hipFree(ctx->d_eval);
-  for (const CtxScratch* sc : {&ctx->denoise, &ctx->light_denoise, &ctx->select, &ctx->tile_list})
+  for (const CtxScratch* sc :
+       {&ctx->order, &ctx->fcolor, &ctx->denoise, &ctx->light_denoise, &ctx->select, &ctx->tile_list})
     if (sc->d) (void)hipFree(sc->d);
   delete ctx;
 }
@@ -2279,35 +2284,53 @@ bool same_shared_uniforms(const rt4_uniforms& a, const rt4_uniforms& b) {
          std::memcmp(a.focus, b.focus, sizeof a.focus) == 0;
 }
 
-// Frames pipelined in one launch (rt4_render_frames_device): per-frame seed and part of job 0.
-struct FramePlan {
-  int32_t n;
-  const int32_t* seeds;
-  const float* parts;
-};
+// The camera, region and tiling of one image's JobArgs; returns its 8x8 tiles (none for an empty region).
+unsigned fill_job(JobArgs& J, const rt4_uniforms& u, const rt4_region& reg, int64_t row_stride_px) {
+  std::memcpy(J.resolution, u.resolution, sizeof J.resolution);
+  std::memcpy(J.mtr_sizes, u.mtr_sizes, sizeof J.mtr_sizes);
+  std::memcpy(J.vec_to_mtr, u.vec_to_mtr, sizeof J.vec_to_mtr);
+  std::memcpy(J.top_drct, u.top_drct, sizeof J.top_drct);
+  std::memcpy(J.right_drct, u.right_drct, sizeof J.right_drct);
+  J.reg = reg;
+  J.row_stride_px = row_stride_px;
+  const bool empty = reg.w == 0 || reg.h == 0;
+  J.tiles_x = empty ? 1u : static_cast<unsigned>((reg.w + 7) / 8);
+  return empty ? 0u : J.tiles_x * static_cast<unsigned>((reg.h + 7) / 8);
+}
 
-// A launch into a light accumulator (rt4_render_light_device, rt4_light.h): its frames' light sums go to the
-// frame-colour scratch whatever their number, and rt4_fold_light_kernel folds them in place of rt4_fold_frames_kernel.
-struct LightTarget {
-  rt4_light_px* light;
-  int64_t row_stride_px;
-};
-__global__ __launch_bounds__(256) void rt4_fold_light_kernel(const KernelArgs a, rt4_light_px* light, int64_t light_stride,
-                                      unsigned long long* count_src, unsigned long long* count_dst);
 // A light launch of listed tiles only (rt4_render_light_tiles_device, rt4_light_tiles.h): n tile numbers of job 0 on the
 // device. The trace kernel gets a clamped copy as its order (stage_tile_list) and the fold runs over the listed tiles.
 struct TileList {
   const uint32_t* d_tiles;
   int32_t n;
 };
+// A launch into a light accumulator (rt4_render_light_device, rt4_light.h): its frames' light sums go to the
+// frame-colour scratch whatever their number, and rt4_fold_light_kernel folds them in place of rt4_fold_frames_kernel.
+// Only such a launch can have a tile list.
+struct LightTarget {
+  rt4_light_px* light;
+  int64_t row_stride_px;
+  const TileList* tiles;  // or null: every tile
+};
+__global__ __launch_bounds__(256) void rt4_fold_light_kernel(const KernelArgs a, rt4_light_px* light, int64_t light_stride,
+                                      unsigned long long* count_src, unsigned long long* count_dst);
+// The one mode of launch_jobs next to a single frame of its jobs: n frames of job 0 pipelined through the frame-colour
+// scratch (rt4_render_frames_device: n >= 2), per-frame seed and part, folded into the frame or, with a light target
+// (n >= 1), into its accumulator.
+struct FramePlan {
+  int32_t n;
+  const int32_t* seeds;
+  const float* parts;
+  const LightTarget* light;  // or null: the colour fold
+};
 int stage_tile_list(rt4_context* ctx, const TileList& tl, unsigned tiles, KernelArgs& a, hipStream_t s, char* err,
                     size_t errlen);
 void launch_fold_light_tiles(const KernelArgs& a, const LightTarget& lt, hipStream_t s);
 
+bool primary_reuse(const rt4_context* ctx) { return (ctx->flags & RT4_FLAG_PRIMARY_REUSE) && ctx->shape != GENERIC; }
 // The trace kernel a launch of the context runs: its scene's shape, the sampler table, primary reuse.
 TraceFn trace_fn_of(const rt4_context* ctx) {
-  const bool reuse = (ctx->flags & RT4_FLAG_PRIMARY_REUSE) && ctx->shape != GENERIC;
-  return variant_for(ctx->shape).trace[ctx->d_wlut ? 1 : 0][reuse ? 1 : 0];
+  return variant_for(ctx->shape).trace[ctx->d_wlut ? 1 : 0][primary_reuse(ctx) ? 1 : 0];
 }
 
 // Blocks per CU the trace kernel fn holds (occupancy query, cached per kernel).
@@ -2349,15 +2372,16 @@ int ensure_overlap_buffer(rt4_context* ctx, unsigned k, size_t need, char* err, 
   return RT4_OK;
 }
 
-int launch_jobs(rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, int32_t format,
-                unsigned long long* d_counter, void* stream, char* err, size_t errlen, const FramePlan* fp = nullptr,
-                const LightTarget* lt = nullptr, const TileList* tl = nullptr) {
+// ---- launch_jobs, step by step ------------------------------------------------------------------
+// Step 1, host code only: the checks of a launch and its KernelArgs (order, order_ends and fcolor stay null for the
+// later steps). *n_tiles: the 8x8 tiles of one frame of all jobs; none: nothing to launch.
+int build_launch_args(const rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, int32_t format,
+                      const FramePlan* fp, KernelArgs& a, unsigned* n_tiles, char* err, size_t errlen) {
   if (!ctx || !jobs) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
   if (!ctx->has_scene) return rt4_set_err(err, errlen, "context has no scene (rt4_context_set_scene)"), RT4_ERR_ARG;
   if (n_jobs < 1 || n_jobs > RT4_MAX_SECTIONS)
     return rt4_set_err(err, errlen, "n_jobs %d not in [1, %d]", n_jobs, RT4_MAX_SECTIONS), RT4_ERR_ARG;
   if (rt4_frame_format_bytes(format) == 0) return rt4_set_err(err, errlen, "unknown frame format %d", format), RT4_ERR_ARG;
-  KernelArgs a;
   std::memset(&a, 0, sizeof a);
   const rt4_uniforms& u0 = jobs[0].u;
   a.seed = u0.seed;
@@ -2378,45 +2402,56 @@ int launch_jobs(rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, i
     if (!same_shared_uniforms(jb.u, u0))
       return rt4_set_err(err, errlen, "job %d: seed/samples/reflections/small_indent/part/k/focus differ from job 0", q),
              RT4_ERR_ARG;
-    const bool empty = jb.region.w == 0 || jb.region.h == 0;
-    if (!empty && !jb.d_frame) return rt4_set_err(err, errlen, "job %d: NULL frame", q), RT4_ERR_ARG;
+    if (jb.region.w != 0 && jb.region.h != 0 && !jb.d_frame)
+      return rt4_set_err(err, errlen, "job %d: NULL frame", q), RT4_ERR_ARG;
     JobArgs& J = a.jobs[q];
-    std::memcpy(J.resolution, jb.u.resolution, sizeof J.resolution);
-    std::memcpy(J.mtr_sizes, jb.u.mtr_sizes, sizeof J.mtr_sizes);
-    std::memcpy(J.vec_to_mtr, jb.u.vec_to_mtr, sizeof J.vec_to_mtr);
-    std::memcpy(J.top_drct, jb.u.top_drct, sizeof J.top_drct);
-    std::memcpy(J.right_drct, jb.u.right_drct, sizeof J.right_drct);
-    J.reg = jb.region;
     J.frame = jb.d_frame;
-    J.row_stride_px = jb.row_stride_px;
-    J.tiles_x = empty ? 1u : static_cast<unsigned>((jb.region.w + 7) / 8);
-    const unsigned t = empty ? 0u : J.tiles_x * static_cast<unsigned>((jb.region.h + 7) / 8);
     J.tile_base = tiles;
-    tiles += t;
+    tiles += fill_job(J, jb.u, jb.region, jb.row_stride_px);
   }
+  *n_tiles = tiles;
   if (tiles == 0) return RT4_OK;
   a.total = tiles * 64u;
   a.n_frames = 1;
-  const bool frames = fp && (fp->n > 1 || lt);  // a light launch of one frame goes through the scratch too
-  if (frames) {
-    if (n_jobs != 1 || fp->n > RT4_MAX_FRAMES || a.jobs[0].reg.w > 8191 || a.jobs[0].reg.h > 8191 ||
-        static_cast<uint64_t>(tiles) * 64u * static_cast<uint64_t>(fp->n) >= (1ull << 31))
-      return rt4_set_err(err, errlen, "pipelined frames: bad frame plan"), RT4_ERR_ARG;
-    a.n_frames = fp->n;
-    a.frame_tiles = tiles;
-    a.total = tiles * 64u * static_cast<unsigned>(fp->n);
-    if (tl) {  // the queue hands out the listed tiles only; `tiles` still sizes the checks above and the scratch
-      if (!lt || tl->n < 1 || static_cast<unsigned>(tl->n) > tiles)
-        return rt4_set_err(err, errlen, "tile list: bad length"), RT4_ERR_ARG;
-      a.frame_tiles = static_cast<unsigned>(tl->n);
-      a.total = a.frame_tiles * 64u * static_cast<unsigned>(fp->n);
-    }
-    for (int f = 0; f < fp->n; f++) {
-      a.frame_seed[f] = fp->seeds[f];
-      a.frame_part[f] = fp->parts[f];
-    }
+  if (primary_reuse(ctx)) a.eval_counter = ctx->d_eval;
+  if (!fp) return RT4_OK;
+  // (a plan of one frame is a light launch: it goes through the scratch too)
+  if (n_jobs != 1 || fp->n < (fp->light ? 1 : 2) || fp->n > RT4_MAX_FRAMES || a.jobs[0].reg.w > 8191 ||
+      a.jobs[0].reg.h > 8191 || static_cast<uint64_t>(tiles) * 64u * static_cast<uint64_t>(fp->n) >= (1ull << 31))
+    return rt4_set_err(err, errlen, "pipelined frames: bad frame plan"), RT4_ERR_ARG;
+  a.n_frames = fp->n;
+  a.frame_tiles = tiles;
+  if (const TileList* tl = fp->light ? fp->light->tiles : nullptr) {
+    // the queue hands out the listed tiles only; `tiles` still sizes the checks above and the scratch
+    if (tl->n < 1 || static_cast<unsigned>(tl->n) > tiles)
+      return rt4_set_err(err, errlen, "tile list: bad length"), RT4_ERR_ARG;
+    a.frame_tiles = static_cast<unsigned>(tl->n);
   }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  a.total = a.frame_tiles * 64u * static_cast<unsigned>(fp->n);
+  for (int f = 0; f < fp->n; f++) {
+    a.frame_seed[f] = fp->seeds[f];
+    a.frame_part[f] = fp->parts[f];
+  }
+  return RT4_OK;
+}
+
+// What plan_launch decides once for the later steps of a launch.
+struct LaunchPlan {
+  bool overlap;      // the trace on a side stream into a slot buffer, its fold on the caller's stream
+  bool deep;         // an overlapped launch in the rotation of RT4_OVERLAP_SLOTS; else that of RT4_OVERLAP_BIG
+  unsigned slot;     // launch_seq % RT4_OVERLAP_SLOTS: seq_done, traced and the count slot
+  unsigned rot;      // the launch's place in its rotation: its slot buffer and its side stream
+  hipStream_t s;     // the caller's stream
+  hipStream_t ts;    // the trace kernel's stream: the side stream, or s
+  unsigned blocks;   // of the trace kernel
+  unsigned long long* count;  // where the trace counts: the count slot, or the caller's counter
+};
+
+// Step 2: the launch's shape. Owns the occupancy query, the slot buffer (a frame it cannot allocate runs serially) and
+// the lazy creation of the side stream; an overlapped launch's fcolor, fc_base and frame_part[0] are set here.
+int plan_launch(rt4_context* ctx, KernelArgs& a, bool frames, hipStream_t s, unsigned long long* d_counter,
+                LaunchPlan& p, char* err, size_t errlen) {
+  const int32_t n_jobs = a.n_jobs;
   // Overlapped single frames: one image, one frame, a region the frame-colour pixel word
   // holds; the trace goes to a side stream and its frame colours to a slot buffer, the fold to the caller's
   // stream, so this frame's trace fills the GPU while the previous one drains.
@@ -2428,182 +2463,203 @@ int launch_jobs(rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, i
     small_regions = small_regions && a.jobs[q].reg.w <= 8191 && a.jobs[q].reg.h <= 8191;
     npx_all += static_cast<size_t>(a.jobs[q].reg.w) * static_cast<size_t>(a.jobs[q].reg.h);
   }
-  bool overlap = RT4_OVERLAP_FRAMES && !(ctx->flags & RT4_FLAG_SERIAL_FRAMES) && !frames && small_regions &&
-                 npx_all < (size_t(1) << 31);
-  const unsigned slot = ctx->launch_seq % RT4_OVERLAP_SLOTS;
-  const Variant& v = variant_for(ctx->shape);
-  const bool reuse = (ctx->flags & RT4_FLAG_PRIMARY_REUSE) && ctx->shape != GENERIC;
-  const TraceFn fn = trace_fn_of(ctx);
+  p.overlap = RT4_OVERLAP_FRAMES && !(ctx->flags & RT4_FLAG_SERIAL_FRAMES) && !frames && small_regions &&
+              npx_all < (size_t(1) << 31);
+  p.slot = ctx->launch_seq % RT4_OVERLAP_SLOTS;
+  p.s = p.ts = s;
   // grid: what the device holds at once; later blocks would only find the queue empty
   int per_cu = 0;
-  {
-    const int st = occupancy_of(ctx, fn, &per_cu, err, errlen);
-    if (st != RT4_OK) return st;
-  }
+  const int st = occupancy_of(ctx, trace_fn_of(ctx), &per_cu, err, errlen);
+  if (st != RT4_OK) return st;
   const long long items = static_cast<long long>(a.total >> 6);  // tiles of all jobs (and frames)
   // an overlapped frame with fewer tiles than the chip holds waves runs deep: up to RT4_OVERLAP_SLOTS in flight
-  const bool deep = overlap && overlap_deep(ctx, items, per_cu);
-  if (overlap) {
-    const int st = ensure_overlap_buffer(ctx, deep ? slot : ctx->launch_seq % RT4_OVERLAP_BIG, npx_all * sizeof(float4),
-                                         err, errlen);
-    if (st == kSlotNoMem) overlap = false;  // no memory for the slot buffer: this frame runs serially
-    else if (st != RT4_OK) return st;
-  }
-  hipStream_t ts = s;  // the trace kernel's stream
-  if (overlap) {
-    for (int q = 1; q < n_jobs; q++)
-      a.jobs[q].fc_base = a.jobs[q - 1].fc_base + static_cast<unsigned>(a.jobs[q - 1].reg.w) * static_cast<unsigned>(a.jobs[q - 1].reg.h);
-    a.fcolor = static_cast<float4*>(ctx->d_ofcolor[deep ? slot : ctx->launch_seq % RT4_OVERLAP_BIG]);
-    a.frame_part[0] = a.part;
+  p.deep = p.overlap && overlap_deep(ctx, items, per_cu);
+  p.rot = p.deep ? p.slot : ctx->launch_seq % RT4_OVERLAP_BIG;
+  if (p.overlap) {
+    const int sb = ensure_overlap_buffer(ctx, p.rot, npx_all * sizeof(float4), err, errlen);
+    // no memory for the slot buffer: this frame runs serially (p.deep stays: the waits of the rotation it was meant for)
+    if (sb == kSlotNoMem) p.overlap = false;
+    else if (sb != RT4_OK) return sb;
   }
   int bpc = per_cu > 0 ? per_cu : 1;
   const unsigned long long frame_work = static_cast<unsigned long long>(a.total) * static_cast<unsigned>(a.samples) *
                                        static_cast<unsigned>(a.reflections_amount + 1);
-  if (overlap && frame_work <= RT4_OVERLAP_SHORT_WORK) bpc = bpc > RT4_OVERLAP_GRID_LESS ? bpc - RT4_OVERLAP_GRID_LESS : 1;
+  if (p.overlap && frame_work <= RT4_OVERLAP_SHORT_WORK) bpc = bpc > RT4_OVERLAP_GRID_LESS ? bpc - RT4_OVERLAP_GRID_LESS : 1;
   long long blocks = static_cast<long long>(ctx->n_cu) * bpc;
-  if (overlap) {
-    const unsigned sidx = ctx->launch_seq % (deep ? RT4_OVERLAP_SLOTS : RT4_OVERLAP_BIG);
-    if (!ctx->side[sidx]) {
-      if (RT4_SIDE_LOW_PRIORITY) {
-        int least = 0, greatest = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(hipStreamCreateWithPriority(&ctx->side[sidx], hipStreamNonBlocking, least));
-      } else {
-        HIP_TRY(hipStreamCreateWithFlags(&ctx->side[sidx], hipStreamNonBlocking));
-      }
-    }
-    ts = ctx->side[sidx];
-  }
   if (blocks > (items + 3) / 4) blocks = (items + 3) / 4;  // >= one tile per wave
-  if (blocks < 1) blocks = 1;
-  a.order = nullptr;
-  a.order_ends = nullptr;
-  if (reuse) a.eval_counter = ctx->d_eval;
+  p.blocks = static_cast<unsigned>(blocks < 1 ? 1 : blocks);
+  p.count = p.overlap ? ctx->d_ocount + p.slot : d_counter;
+  if (!p.overlap) return RT4_OK;
+  for (int q = 1; q < n_jobs; q++)
+    a.jobs[q].fc_base = a.jobs[q - 1].fc_base + static_cast<unsigned>(a.jobs[q - 1].reg.w) * static_cast<unsigned>(a.jobs[q - 1].reg.h);
+  a.fcolor = static_cast<float4*>(ctx->d_ofcolor[p.rot]);
+  a.frame_part[0] = a.part;
+  if (!ctx->side[p.rot]) {
+    if (RT4_SIDE_LOW_PRIORITY) {
+      int least = 0, greatest = 0;
+      HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+      HIP_TRY(hipStreamCreateWithPriority(&ctx->side[p.rot], hipStreamNonBlocking, least));
+    } else {
+      HIP_TRY(hipStreamCreateWithFlags(&ctx->side[p.rot], hipStreamNonBlocking));
+    }
+  }
+  p.ts = ctx->side[p.rot];
+  return RT4_OK;
+}
+
+// Step 3: the launch behind the context's earlier ones, on the trace kernel's stream.
+int order_behind_earlier(rt4_context* ctx, const LaunchPlan& p, char* err, size_t errlen) {
   // The tile order buffer is one per context: a launch on another stream than the previous one
   // waits for it (launches of one context run in submission order). So does an overlapped launch that
   // switches between the deep and the big rotation (they share slot buffers 0 .. RT4_OVERLAP_BIG - 1).
-  if (ctx->launched && (s != ctx->last_stream || (overlap && ctx->overlapped && deep != ctx->last_deep)))
-    HIP_TRY(hipStreamWaitEvent(ts, ctx->done, 0));
+  if (ctx->launched && (p.s != ctx->last_stream || (p.overlap && ctx->overlapped && p.deep != ctx->last_deep)))
+    HIP_TRY(hipStreamWaitEvent(p.ts, ctx->done, 0));
   // launch s - S is complete before launch s starts: its queue word, frame-colour slot and count slot are
   // free again (launches s - S + 1 .. s - 1 may still be draining: that is the overlap)
-  HIP_TRY(hipStreamWaitEvent(ts, ctx->seq_done[slot], 0));
-  if (!deep && RT4_OVERLAP_BIG < RT4_OVERLAP_SLOTS)  // and launch s - RT4_OVERLAP_BIG (a frame that fills the chip)
-    HIP_TRY(hipStreamWaitEvent(ts, ctx->seq_done[(ctx->launch_seq + RT4_OVERLAP_SLOTS - RT4_OVERLAP_BIG) % RT4_OVERLAP_SLOTS], 0));
-  if (frames) {  // the frame colours of a pipelined launch: one scratch buffer per context, grown to the
-    // launch's frames (rt4_context_reserve_frames sizes it for a whole chunk ahead of time)
-    const size_t need = static_cast<size_t>(fp->n) * static_cast<size_t>(a.jobs[0].reg.w) *
-                        static_cast<size_t>(a.jobs[0].reg.h) * sizeof(float4);
-    if (ctx->fcolor_bytes < need) {
-      HIP_TRY(hipStreamSynchronize(s));
-      if (ctx->d_fcolor) (void)hipFree(ctx->d_fcolor);
-      ctx->d_fcolor = nullptr;
-      ctx->fcolor_bytes = 0;
-      HIP_TRY(hipMalloc(&ctx->d_fcolor, need));
-      ctx->fcolor_bytes = need;
-    }
-    a.fcolor = static_cast<float4*>(ctx->d_fcolor);
-  }
+  HIP_TRY(hipStreamWaitEvent(p.ts, ctx->seq_done[p.slot], 0));
+  if (!p.deep && RT4_OVERLAP_BIG < RT4_OVERLAP_SLOTS)  // and launch s - RT4_OVERLAP_BIG (a frame that fills the chip)
+    HIP_TRY(hipStreamWaitEvent(p.ts, ctx->seq_done[(ctx->launch_seq + RT4_OVERLAP_SLOTS - RT4_OVERLAP_BIG) % RT4_OVERLAP_SLOTS], 0));
+  return RT4_OK;
+}
+
+// Step 4, a frame plan's launch: its frame colours in the context's one scratch buffer, grown to the launch's frames
+// (rt4_context_reserve_frames sizes it for a whole chunk ahead of time).
+int frame_scratch(rt4_context* ctx, KernelArgs& a, hipStream_t s, char* err, size_t errlen) {
+  const size_t need = static_cast<size_t>(a.n_frames) * static_cast<size_t>(a.jobs[0].reg.w) *
+                      static_cast<size_t>(a.jobs[0].reg.h) * sizeof(float4);
+  // Growing also waits for `done`: nothing new, s already waits for it or is the stream it was recorded on (step 3).
+  const int st = grow_scratch(ctx, ctx->fcolor, s, need, 1, err, errlen);
+  a.fcolor = static_cast<float4*>(ctx->fcolor.d);
+  return st;
+}
+
 #if RT4_ORDER_PREPASS
-  // Pipelined frames keep row-major order: the longest-first order only shortens the drain at the end
-  // of a launch, which a pipelined launch pays once, and in the main phase row-major measured faster
-  // (config 2 +1.5 %, config 3 +2 %; profiles/r02_ab.txt).
-  if (!frames && !overlap) {
-  if (ctx->order_cap < tiles) {  // a frame larger than any before: grow once (allocates)
-    HIP_TRY(hipStreamSynchronize(s));
-    if (ctx->d_order) (void)hipFree(ctx->d_order);
-    ctx->d_order = nullptr;
-    ctx->order_cap = 0;
+// Step 5, a single serial frame: the longest-first order of its tiles, from the pre-pass or the previous launch.
+// Pipelined frames keep row-major order: the longest-first order only shortens the drain at the end
+// of a launch, which a pipelined launch pays once, and in the main phase row-major measured faster
+// (config 2 +1.5 %, config 3 +2 %; profiles/r02_ab.txt).
+int tile_order(rt4_context* ctx, KernelArgs& a, unsigned tiles, hipStream_t s, char* err, size_t errlen) {
+  if (ctx->order.cap < static_cast<size_t>(tiles) + 2) {  // a frame larger than any before: grow once (allocates)
     ctx->order_valid = false;
-    HIP_TRY(hipMalloc(&ctx->d_order, (static_cast<size_t>(tiles) + 2) * sizeof(unsigned)));
-    ctx->order_cap = tiles;
-  }
-  unsigned* ends = ctx->d_order + ctx->order_cap;
-  // The order depends only on the scene and the primary rays (camera, regions, resolution): a frame
-  // that repeats them (progressive accumulation, a benchmark loop) reuses the previous order.
-  KernelArgs ao = a;  // the order is per frame: one frame's tiles
-  ao.total = tiles * 64u;
-  ao.n_frames = 1;
-  if (!(ctx->order_valid && same_primary_rays(ctx->order_args, ao))) {
-    ctx->order_valid = false;
-    HIP_TRY(hipMemsetAsync(ends, 0, 2 * sizeof(unsigned), s));
-    hipLaunchKernelGGL(v.order, dim3((tiles + 255u) / 256u), dim3(256), 0, s, ctx->d_scene, scene_aux(ctx), ao,
-                       ctx->d_order, ends);
-    HIP_TRY(hipGetLastError());
-    ctx->order_args = ao;
-    ctx->order_valid = true;
-  }
-  a.order = ctx->d_order;
-  a.order_ends = ends;
-  }
-#endif
-  if (tl && frames) {  // behind the waits above: the context's copy of the list is one per context, like d_order
-    const int st = stage_tile_list(ctx, *tl, tiles, a, ts, err, errlen);
+    // (the wait for `done` in it is redundant here as in step 4)
+    const int st = grow_scratch(ctx, ctx->order, s, static_cast<size_t>(tiles) + 2, sizeof(unsigned), err, errlen);
     if (st != RT4_OK) return st;
   }
-  // Queue words rotate; launch s zeroes launch s + S's word (launches up to s + S - 1 may already be running,
-  // s + S starts only after s is complete): no memset between frames.
-  unsigned* q = ctx->d_queue + (ctx->launch_seq % QUEUE_SLOTS);
-  unsigned* q_next = ctx->d_queue + ((ctx->launch_seq + RT4_OVERLAP_SLOTS) % QUEUE_SLOTS);  // zeroed by this launch
-  const unsigned seq = ctx->launch_seq++;
-  if (ctx->q_dirty[seq % QUEUE_SLOTS]) {
-    HIP_TRY(hipMemsetAsync(q, 0, sizeof(unsigned), ts));
-    ctx->q_dirty[seq % QUEUE_SLOTS] = false;
+  unsigned* order = static_cast<unsigned*>(ctx->order.d);
+  unsigned* ends = order + ctx->order.cap - 2;
+  // The order depends only on the scene and the primary rays (camera, regions, resolution): a frame
+  // that repeats them (progressive accumulation, a benchmark loop) reuses the previous order.
+  if (!(ctx->order_valid && same_primary_rays(ctx->order_args, a))) {
+    ctx->order_valid = false;
+    HIP_TRY(hipMemsetAsync(ends, 0, 2 * sizeof(unsigned), s));
+    hipLaunchKernelGGL(variant_for(ctx->shape).order, dim3((tiles + 255u) / 256u), dim3(256), 0, s, ctx->d_scene,
+                       scene_aux(ctx), a, order, ends);
+    HIP_TRY(hipGetLastError());
+    ctx->order_args = a;
+    ctx->order_valid = true;
   }
-  if (overlap) {
+  a.order = order;
+  a.order_ends = ends;
+  return RT4_OK;
+}
+#endif
+
+// Step 7: the launch's sequence number and with it its queue word. Queue words rotate; launch s zeroes launch
+// s + S's word (launches up to s + S - 1 may already be running, s + S starts only after s is complete): no memset
+// between frames, unless a failed launch left this one's word dirty. The last step that can return without having
+// consumed a sequence number.
+int claim_queue_word(rt4_context* ctx, const LaunchPlan& p, unsigned* seq, char* err, size_t errlen) {
+  const unsigned word = ctx->launch_seq % QUEUE_SLOTS;
+  if (ctx->q_dirty[word]) {
+    HIP_TRY(hipMemsetAsync(ctx->d_queue + word, 0, sizeof(unsigned), p.ts));
+    ctx->q_dirty[word] = false;
+  }
+  *seq = ctx->launch_seq++;
+  if (p.overlap) {
     ctx->overlapped = true;
-    ctx->last_deep = deep;
+    ctx->last_deep = p.deep;
   }
-  unsigned long long* count = overlap ? ctx->d_ocount + slot : d_counter;
+  return RT4_OK;
+}
+
+// Step 8: the trace kernel, the fold of a frame plan or of an overlapped launch, the events, and the recovery from a
+// launch that failed.
+int trace_and_fold(rt4_context* ctx, const KernelArgs& a, const LaunchPlan& p, unsigned seq, const FramePlan* fp,
+                   unsigned long long* d_counter, char* err, size_t errlen) {
+  unsigned* q = ctx->d_queue + (seq % QUEUE_SLOTS);
+  unsigned* q_next = ctx->d_queue + ((seq + RT4_OVERLAP_SLOTS) % QUEUE_SLOTS);  // zeroed by this launch
   (void)hipGetLastError();  // a sticky error of an earlier, unrelated call must not be taken for this launch's
-  hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, ts, ctx->d_scene, scene_aux(ctx), a, count,
+  hipLaunchKernelGGL(trace_fn_of(ctx), dim3(p.blocks), dim3(256), 0, p.ts, ctx->d_scene, scene_aux(ctx), a, p.count,
                      ctx->d_wlut, q, q_next);
   hipError_t le = hipGetLastError();
   const bool trace_enqueued = le == hipSuccess;
-  if (le == hipSuccess && overlap) {
-    le = hipEventRecord(ctx->traced[slot], ts);
-    if (le == hipSuccess) le = hipStreamWaitEvent(s, ctx->traced[slot], 0);
+  if (le == hipSuccess && p.overlap) {
+    le = hipEventRecord(ctx->traced[p.slot], p.ts);
+    if (le == hipSuccess) le = hipStreamWaitEvent(p.s, ctx->traced[p.slot], 0);
   }
-  if (le == hipSuccess && (frames || overlap)) {
+  if (le == hipSuccess && (fp || p.overlap)) {
     long long npx = 0;  // the largest image's pixels (blockIdx.y: the section)
-    for (int q = 0; q < n_jobs; q++) npx = std::max(npx, static_cast<long long>(a.jobs[q].reg.w) * a.jobs[q].reg.h);
-    if (lt && tl) {  // the fold of the listed tiles (rt4_light_tiles.h)
-      launch_fold_light_tiles(a, *lt, s);
+    for (int j = 0; j < a.n_jobs; j++) npx = std::max(npx, static_cast<long long>(a.jobs[j].reg.w) * a.jobs[j].reg.h);
+    const LightTarget* lt = fp ? fp->light : nullptr;
+    unsigned long long* count_src = p.overlap ? p.count : nullptr;  // an overlapped launch's fold moves its count
+    unsigned long long* count_dst = p.overlap ? d_counter : nullptr;
+    if (lt && lt->tiles) {  // the fold of the listed tiles (rt4_light_tiles.h)
+      launch_fold_light_tiles(a, *lt, p.s);
     } else if (lt) {  // the light accumulator's fold in place of the colour fold (rt4_light.h)
-      hipLaunchKernelGGL(rt4_fold_light_kernel, dim3(static_cast<unsigned>((npx + 255) / 256)), dim3(256), 0, s, a, lt->light,
-                         lt->row_stride_px, overlap ? count : nullptr, overlap ? d_counter : nullptr);
+      hipLaunchKernelGGL(rt4_fold_light_kernel, dim3(static_cast<unsigned>((npx + 255) / 256)), dim3(256), 0, p.s, a,
+                         lt->light, lt->row_stride_px, count_src, count_dst);
     } else {
-      hipLaunchKernelGGL(rt4_fold_frames_kernel, dim3(static_cast<unsigned>((npx + 255) / 256), static_cast<unsigned>(n_jobs)),
-                         dim3(256), 0, s, a, overlap ? count : nullptr, overlap ? d_counter : nullptr);
+      hipLaunchKernelGGL(rt4_fold_frames_kernel, dim3(static_cast<unsigned>((npx + 255) / 256), static_cast<unsigned>(a.n_jobs)),
+                         dim3(256), 0, p.s, a, count_src, count_dst);
     }
     le = hipGetLastError();
   }
   // Record the events whatever happened: a launch that may have been enqueued still orders the next
-  // launch on another stream behind it (they share d_order / the queue words).
-  const hipError_t re2 = hipEventRecord(ctx->seq_done[slot], s);
-  hipError_t re = hipEventRecord(ctx->done, s);
-  if (re == hipSuccess) re = re2;
-  ctx->last_stream = s;
-  ctx->launched = true;
+  // launch on another stream behind it (they share the tile order / the queue words).
+  const hipError_t re = hipEventRecord(ctx->seq_done[p.slot], p.s);
+  int rc = done_launch(ctx, p.s, err, errlen);
   if (le != hipSuccess) {
     ctx->q_dirty[(seq + RT4_OVERLAP_SLOTS) % QUEUE_SLOTS] = true;  // q_next may not be zeroed: its next user does it
-    if (overlap && trace_enqueued) {
+    if (p.overlap && trace_enqueued) {
       // the trace runs on the side stream but no fold on the caller's stream covers it: wait for it here (the
       // scene, the slot buffer and the queue words stay valid), then clear the count it left in its slot
-      (void)hipStreamSynchronize(ts);
-      (void)hipMemsetAsync(count, 0, sizeof(unsigned long long), s);
+      (void)hipStreamSynchronize(p.ts);
+      (void)hipMemsetAsync(p.count, 0, sizeof(unsigned long long), p.s);
       // the launch that reuses this count slot waits on seq_done[slot]: record it (and done) again behind the
       // memset, so that launch's trace cannot add to the slot before it is cleared
-      (void)hipEventRecord(ctx->seq_done[slot], s);
-      (void)hipEventRecord(ctx->done, s);
+      (void)hipEventRecord(ctx->seq_done[p.slot], p.s);
+      (void)hipEventRecord(ctx->done, p.s);
     }
     rt4_set_err(err, errlen, "trace kernel launch failed: %s", hipGetErrorString(le));
     return RT4_ERR_HIP;
   }
-  if (re != hipSuccess) {
+  if (rc == RT4_OK && re != hipSuccess) {
     rt4_set_err(err, errlen, "hipEventRecord failed: %s", hipGetErrorString(re));
-    return RT4_ERR_HIP;
+    rc = RT4_ERR_HIP;
   }
-  return RT4_OK;
+  return rc;
+}
+
+// One launch of the trace kernel over the jobs' images: a single frame of each, or the frames of a plan.
+int launch_jobs(rt4_context* ctx, const rt4_section_job* jobs, int32_t n_jobs, int32_t format,
+                unsigned long long* d_counter, void* stream, char* err, size_t errlen, const FramePlan* fp = nullptr) {
+  KernelArgs a;
+  LaunchPlan p;
+  unsigned tiles = 0, seq = 0;
+  int st = build_launch_args(ctx, jobs, n_jobs, format, fp, a, &tiles, err, errlen);
+  if (st != RT4_OK || tiles == 0) return st;  // before any HIP call
+  st = plan_launch(ctx, a, fp != nullptr, reinterpret_cast<hipStream_t>(stream), d_counter, p, err, errlen);
+  if (st == RT4_OK) st = order_behind_earlier(ctx, p, err, errlen);
+  if (st == RT4_OK && fp) st = frame_scratch(ctx, a, p.s, err, errlen);
+#if RT4_ORDER_PREPASS
+  if (st == RT4_OK && !fp && !p.overlap) st = tile_order(ctx, a, tiles, p.s, err, errlen);
+#endif
+  // Step 6, behind the waits of step 3: the context's copy of the list is one per context, like the tile order
+  if (st == RT4_OK && fp && fp->light && fp->light->tiles)
+    st = stage_tile_list(ctx, *fp->light->tiles, tiles, a, p.ts, err, errlen);
+  if (st == RT4_OK) st = claim_queue_word(ctx, p, &seq, err, errlen);
+  if (st != RT4_OK) return st;  // no sequence number consumed
+  return trace_and_fold(ctx, a, p, seq, fp, d_counter, err, errlen);
 }
 
 }  // namespace
@@ -2653,15 +2709,13 @@ int rt4_context_reserve_frames(rt4_context* ctx, int32_t w, int32_t h, char* err
   const int32_t cap = rt4_context_frames_per_launch(ctx, w, h);
   if (cap < 2) return RT4_OK;
   const size_t need = static_cast<size_t>(cap) * static_cast<size_t>(w) * static_cast<size_t>(h) * sizeof(float4);
-  if (ctx->fcolor_bytes >= need) return RT4_OK;
+  if (ctx->fcolor.cap >= need) return RT4_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  if (ctx->launched) HIP_TRY(hipEventSynchronize(ctx->done));
-  if (ctx->d_fcolor) (void)hipFree(ctx->d_fcolor);
-  ctx->d_fcolor = nullptr;
-  ctx->fcolor_bytes = 0;
-  HIP_TRY(hipMalloc(&ctx->d_fcolor, need));
-  HIP_TRY(hipMemset(ctx->d_fcolor, 0, need));  // first touch here, not in the first pipelined launch
-  ctx->fcolor_bytes = need;
+  // No stream here: growing waits for the context's launches (done), as before, and for the null stream, on which
+  // this set-up call's own memset runs.
+  const int st = grow_scratch(ctx, ctx->fcolor, nullptr, need, 1, err, errlen);
+  if (st != RT4_OK) return st;
+  HIP_TRY(hipMemset(ctx->fcolor.d, 0, need));  // first touch here, not in the first pipelined launch
   return RT4_OK;
 }
 
@@ -2722,7 +2776,7 @@ int rt4_render_frames_device(rt4_context* ctx, const rt4_uniforms* u, int32_t n_
         seeds[f] = u[f0 + f].seed;
         parts[f] = u[f0 + f].part;
       }
-      const FramePlan fp{n, seeds, parts};
+      const FramePlan fp{n, seeds, parts, nullptr};
       st = launch_jobs(ctx, &job, 1, format, d_counter, stream, err, errlen, &fp);
     }
     if (st != RT4_OK) return st;
@@ -2752,35 +2806,19 @@ int rt4_render_host_ex(rt4_context* ctx, const rt4_uniforms* u, const rt4_region
   if (n_intersections) *n_intersections = 0;
   if (region->w == 0 || region->h == 0) return RT4_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  const size_t bytes = (static_cast<size_t>(region->h - 1) * row_stride_px + static_cast<size_t>(region->w)) * px_bytes;
-  void* d = nullptr;
-  unsigned long long* dc = nullptr;
-  HIP_TRY(hipMalloc(&d, bytes));
-  hipError_t e = hipMalloc(&dc, sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemcpy(d, frame, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(dc, 0, sizeof(unsigned long long));
-  if (e != hipSuccess) {
-    (void)hipFree(d);
-    if (dc) (void)hipFree(dc);
-    rt4_set_err(err, errlen, "render_host staging failed: %s", hipGetErrorString(e));
-    return RT4_ERR_HIP;
-  }
-  st = rt4_render_device_ex(ctx, u, region, d, format, row_stride_px, dc, nullptr, err, errlen);
-  if (st == RT4_OK) {
-    e = hipDeviceSynchronize();
-    unsigned long long cnt = 0;
-    if (e == hipSuccess) e = hipMemcpy(frame, d, bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&cnt, dc, sizeof(cnt), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-      rt4_set_err(err, errlen, "render_host failed: %s", hipGetErrorString(e));
-      st = RT4_ERR_HIP;
-    } else if (n_intersections) {
-      *n_intersections = cnt;
-    }
-  }
-  (void)hipFree(d);
-  (void)hipFree(dc);
-  return st;
+  HostStage d, dc;  // the caller's frame first: the render blends into it, and its row padding comes back as it went
+  hipError_t e = d.up(frame, image_span(row_stride_px, region->w, region->h) * static_cast<size_t>(px_bytes));
+  if (e == hipSuccess) e = alloc_zeroed(&dc.d, sizeof(unsigned long long));
+  if (e != hipSuccess) return rt4_set_err(err, errlen, "render_host staging failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
+  st = rt4_render_device_ex(ctx, u, region, d.d, format, row_stride_px, dc.as<unsigned long long>(), nullptr, err, errlen);
+  if (st != RT4_OK) return st;
+  e = hipDeviceSynchronize();
+  unsigned long long cnt = 0;
+  if (e == hipSuccess) e = d.down(frame);
+  if (e == hipSuccess) e = hipMemcpy(&cnt, dc.d, sizeof(cnt), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return rt4_set_err(err, errlen, "render_host failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
+  if (n_intersections) *n_intersections = cnt;
+  return RT4_OK;
 }
 
 int rt4_render_host(rt4_context* ctx, const rt4_uniforms* u, const rt4_region* region, float* rgba,
@@ -2788,7 +2826,7 @@ int rt4_render_host(rt4_context* ctx, const rt4_uniforms* u, const rt4_region* r
   return rt4_render_host_ex(ctx, u, region, rgba, RT4_FRAME_RGBA32F, row_stride_px, n_intersections, err, errlen);
 }
 
-uint64_t rt4_context_frame_scratch_bytes(const rt4_context* ctx) { return ctx ? ctx->fcolor_bytes : 0u; }
+uint64_t rt4_context_frame_scratch_bytes(const rt4_context* ctx) { return ctx ? ctx->fcolor.cap : 0u; }
 
 int rt4_bands_unpermute_device(const void* d_gathered, void* d_image, int32_t width, int32_t height, int32_t world,
                                int32_t band, int32_t rows_max, int32_t format, void* stream, char* err, size_t errlen) {
@@ -2823,43 +2861,33 @@ int rt4_debug_eval(rt4_context* ctx, int fn, const float* in, float* out, int32_
   if (!ctx || !in || !out || n < 0) return rt4_set_err(err, errlen, "bad argument"), RT4_ERR_ARG;
   if (n == 0) return RT4_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  float *din = nullptr, *dout = nullptr;
-  int32_t* daux = nullptr;
-  HIP_TRY(hipMalloc(&din, n * sizeof(float)));
-  hipError_t e = hipMalloc(&dout, n * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&daux, n * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMemcpy(din, in, n * sizeof(float), hipMemcpyHostToDevice);
+  HostStage din, dout, daux;
+  hipError_t e = din.up(in, n * sizeof(float));
+  if (e == hipSuccess) e = dout.up(nullptr, n * sizeof(float));
+  if (e == hipSuccess) e = daux.up(nullptr, n * sizeof(int32_t));
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(rt4_eval_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, 0, fn, din, dout,
-                       daux, n);
+    hipLaunchKernelGGL(rt4_eval_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, 0, fn, din.as<float>(),
+                       dout.as<float>(), daux.as<int32_t>(), n);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, dout, n * sizeof(float), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && aux) e = hipMemcpy(aux, daux, n * sizeof(int32_t), hipMemcpyDeviceToHost);
-  (void)hipFree(din);
-  if (dout) (void)hipFree(dout);
-  if (daux) (void)hipFree(daux);
-  if (e != hipSuccess) {
-    rt4_set_err(err, errlen, "debug_eval failed: %s", hipGetErrorString(e));
-    return RT4_ERR_HIP;
-  }
+  if (e == hipSuccess) e = dout.down(out);
+  if (e == hipSuccess && aux) e = daux.down(aux);
+  if (e != hipSuccess) return rt4_set_err(err, errlen, "debug_eval failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
   return RT4_OK;
 }
 
 int rt4_debug_verify_sqrt(rt4_context* ctx, uint64_t* mismatches, char* err, size_t errlen) {
   if (!ctx || !mismatches) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
-  unsigned long long* d = nullptr;
-  HIP_TRY(hipMalloc(&d, sizeof(unsigned long long)));
-  hipError_t e = hipMemset(d, 0, sizeof(unsigned long long));
+  HostStage d;
+  hipError_t e = alloc_zeroed(&d.d, sizeof(unsigned long long));
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(rt4_verify_sqrt_kernel, dim3(65536), dim3(256), 0, 0, d);
+    hipLaunchKernelGGL(rt4_verify_sqrt_kernel, dim3(65536), dim3(256), 0, 0, d.as<unsigned long long>());
     e = hipGetLastError();
   }
   unsigned long long v = 0;
-  if (e == hipSuccess) e = hipMemcpy(&v, d, sizeof v, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
+  if (e == hipSuccess) e = hipMemcpy(&v, d.d, sizeof v, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return rt4_set_err(err, errlen, "verify_sqrt failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
   *mismatches = v;
   return RT4_OK;
@@ -2897,20 +2925,14 @@ int rt4_debug_sky_threshold(rt4_context* ctx, float ang, int32_t full, float* c_
   if (!ctx || !c_min) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> lock(g_verify_mu);
-  const bool small = !full && ang <= 1.0f;
-  const uint32_t init = 0xFFFFFFFFu, lo = small ? 0x3F000001u : 0u;
-  const uint64_t count = small ? (0x3F800000ull - 0x3F000001ull + 1ull) : (1ull << 32);
+  const SkySweep w = sky_sweep(ang, full != 0);
+  const uint32_t init = 0xFFFFFFFFu;
   HIP_TRY(hipMemcpy(ctx->d_scratch, &init, sizeof init, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(rt4_sky_threshold_kernel, dim3(small ? 512 : 65536), dim3(256), 0, 0, ang, lo, count, ctx->d_scratch);
+  hipLaunchKernelGGL(rt4_sky_threshold_kernel, dim3(w.blocks), dim3(256), 0, 0, ang, w.lo, w.count, ctx->d_scratch);
   HIP_TRY(hipGetLastError());
   uint32_t best = 0;
   HIP_TRY(hipMemcpy(&best, ctx->d_scratch, sizeof best, hipMemcpyDeviceToHost));
-  if (best == 0xFFFFFFFFu) {
-    *c_min = NAN;
-  } else {
-    const uint32_t bits = (best & 0x80000000u) ? (best & 0x7FFFFFFFu) : ~best;
-    std::memcpy(c_min, &bits, 4);
-  }
+  *c_min = best == 0xFFFFFFFFu ? NAN : order_key_float(best);
   return RT4_OK;
 }
 
@@ -2920,26 +2942,20 @@ int rt4_debug_find_intersection(rt4_context* ctx, const float* rays, float* out,
   if (!ctx->has_scene) return rt4_set_err(err, errlen, "context has no scene"), RT4_ERR_ARG;
   if (n == 0) return RT4_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  float *dr = nullptr, *dout = nullptr, *dcol = nullptr;
-  HIP_TRY(hipMalloc(&dr, n * 8 * sizeof(float)));
-  hipError_t e = hipMalloc(&dout, n * 8 * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&dcol, n * 3 * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(dr, rays, n * 8 * sizeof(float), hipMemcpyHostToDevice);
+  HostStage dr, dout, dcol;
+  hipError_t e = dr.up(rays, n * 8 * sizeof(float));
+  if (e == hipSuccess) e = dout.up(nullptr, n * 8 * sizeof(float));
+  if (e == hipSuccess) e = dcol.up(nullptr, n * 3 * sizeof(float));
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(variant_for(ctx->shape).find, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, 0, ctx->d_scene, scene_aux(ctx),
-                       dr, dout, dcol, n);
+    hipLaunchKernelGGL(variant_for(ctx->shape).find, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, 0,
+                       ctx->d_scene, scene_aux(ctx), dr.as<float>(), dout.as<float>(), dcol.as<float>(), n);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, dout, n * 8 * sizeof(float), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(out_color, dcol, n * 3 * sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(dr);
-  if (dout) (void)hipFree(dout);
-  if (dcol) (void)hipFree(dcol);
-  if (e != hipSuccess) {
-    rt4_set_err(err, errlen, "debug_find_intersection failed: %s", hipGetErrorString(e));
-    return RT4_ERR_HIP;
-  }
+  if (e == hipSuccess) e = dout.down(out);
+  if (e == hipSuccess) e = dcol.down(out_color);
+  if (e != hipSuccess)
+    return rt4_set_err(err, errlen, "debug_find_intersection failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
   return RT4_OK;
 }
 
@@ -2948,23 +2964,17 @@ int rt4_debug_final_light(rt4_context* ctx, const float* drct, float* out, int64
   if (!ctx->has_scene) return rt4_set_err(err, errlen, "context has no scene"), RT4_ERR_ARG;
   if (n == 0) return RT4_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  float *dd = nullptr, *dout = nullptr;
-  HIP_TRY(hipMalloc(&dd, n * 4 * sizeof(float)));
-  hipError_t e = hipMalloc(&dout, n * 3 * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(dd, drct, n * 4 * sizeof(float), hipMemcpyHostToDevice);
+  HostStage dd, dout;
+  hipError_t e = dd.up(drct, n * 4 * sizeof(float));
+  if (e == hipSuccess) e = dout.up(nullptr, n * 3 * sizeof(float));
   if (e == hipSuccess) {
     hipLaunchKernelGGL(rt4_final_light_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, 0, ctx->d_scene,
-                       scene_aux(ctx), dd, dout, n);
+                       scene_aux(ctx), dd.as<float>(), dout.as<float>(), n);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, dout, n * 3 * sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(dd);
-  if (dout) (void)hipFree(dout);
-  if (e != hipSuccess) {
-    rt4_set_err(err, errlen, "debug_final_light failed: %s", hipGetErrorString(e));
-    return RT4_ERR_HIP;
-  }
+  if (e == hipSuccess) e = dout.down(out);
+  if (e != hipSuccess) return rt4_set_err(err, errlen, "debug_final_light failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
   return RT4_OK;
 }
 
@@ -2973,24 +2983,17 @@ int rt4_debug_bound_skip(rt4_context* ctx, const float* rays, uint32_t* out_mask
   if (!ctx->has_scene) return rt4_set_err(err, errlen, "context has no scene"), RT4_ERR_ARG;
   if (n == 0) return RT4_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  float* dr = nullptr;
-  uint32_t* dout = nullptr;
-  HIP_TRY(hipMalloc(&dr, n * 8 * sizeof(float)));
-  hipError_t e = hipMalloc(&dout, n * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemcpy(dr, rays, n * 8 * sizeof(float), hipMemcpyHostToDevice);
+  HostStage dr, dout;
+  hipError_t e = dr.up(rays, n * 8 * sizeof(float));
+  if (e == hipSuccess) e = dout.up(nullptr, n * sizeof(uint32_t));
   if (e == hipSuccess) {
     hipLaunchKernelGGL(rt4_bound_skip_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, 0, ctx->d_scene,
-                       scene_aux(ctx), dr, dout, n);
+                       scene_aux(ctx), dr.as<float>(), dout.as<uint32_t>(), n);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out_mask, dout, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-  (void)hipFree(dr);
-  if (dout) (void)hipFree(dout);
-  if (e != hipSuccess) {
-    rt4_set_err(err, errlen, "debug_bound_skip failed: %s", hipGetErrorString(e));
-    return RT4_ERR_HIP;
-  }
+  if (e == hipSuccess) e = dout.down(out_mask);
+  if (e != hipSuccess) return rt4_set_err(err, errlen, "debug_bound_skip failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
   return RT4_OK;
 }
 
@@ -3004,8 +3007,7 @@ int rt4_debug_sqrt_thresholds(float r, float* gt, float* lt) {
 }  // extern "C"
 
 // ==================================================================================== G-buffer, denoiser
-// The layer the G-buffer entry points below and every post pass share, then the passes.
-#include "rt4_post.h"
+// The post passes (over rt4_post.h, included with the context), then the G-buffer entry points.
 #include "rt4_denoise.h"
 #include "rt4_temporal.h"
 #include "rt4_upscale.h"
@@ -3030,17 +3032,8 @@ int rt4_render_gbuffer_device(rt4_context* ctx, const rt4_uniforms* u, const rt4
   if (region->w == 0 || region->h == 0) return RT4_OK;
   GbufArgs g;
   std::memset(&g, 0, sizeof g);
-  JobArgs& J = g.J;
-  std::memcpy(J.resolution, u->resolution, sizeof J.resolution);
-  std::memcpy(J.mtr_sizes, u->mtr_sizes, sizeof J.mtr_sizes);
-  std::memcpy(J.vec_to_mtr, u->vec_to_mtr, sizeof J.vec_to_mtr);
-  std::memcpy(J.top_drct, u->top_drct, sizeof J.top_drct);
-  std::memcpy(J.right_drct, u->right_drct, sizeof J.right_drct);
+  g.tiles = fill_job(g.J, *u, *region, row_stride_px);
   std::memcpy(g.focus, u->focus, sizeof g.focus);
-  J.reg = *region;
-  J.row_stride_px = row_stride_px;
-  J.tiles_x = static_cast<unsigned>((region->w + 7) / 8);
-  g.tiles = J.tiles_x * static_cast<unsigned>((region->h + 7) / 8);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   return post_launch(ctx, s, "G-buffer kernel", err, errlen, [&] {
     hipLaunchKernelGGL(variant_for(ctx->shape).gbuffer, dim3((g.tiles + 3u) / 4u), dim3(256), 0, s, ctx->d_scene,

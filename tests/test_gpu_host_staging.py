@@ -93,6 +93,20 @@ def test_render_gbuffer_host(rt4, tracer_lut, sphere):
 
 
 @pytest.mark.parametrize("fmt", [0, 2], ids=["f32", "rgba8"])
+def test_render_host_ex(rt4, tracer_lut, sphere, fmt):
+    """The render blends into the frame it is given: the caller's image goes up first, padded rows and all."""
+    u, reg, _, _, _ = sphere
+    start = random_frame(rt4.FRAME_NUMPY[fmt], H, W, 11)
+    plain = start.copy()
+    n_plain = tracer_lut.render_host_ex(u, reg, plain, fmt)
+    assert image_bytes(plain, W) != image_bytes(start, W)
+    frame = wide(start)
+    n = tracer_lut.render_host_ex(u, reg, frame, fmt)
+    assert n == n_plain and n > 0
+    check_outputs([frame], [plain])
+
+
+@pytest.mark.parametrize("fmt", [0, 2], ids=["f32", "rgba8"])
 def test_denoise_host(rt4, tracer_lut, fmt):
     dt = rt4.FRAME_NUMPY[fmt]
     frame, g = random_frame(dt, H, W, 1), random_gbuffer(rt4, H, W, 2)
