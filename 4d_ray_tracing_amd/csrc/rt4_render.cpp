@@ -173,6 +173,26 @@ struct ShardJob {
   std::function<int(rt4_context* ctx, const void* gathered, void* image, hipStream_t stream, char* err, size_t errlen)> finish;
 };
 
+// The test switches of a multi-GPU run, read once (shard_hooks): --rehearse, RT4_RENDER_FAIL_RANK (this rank's set-up
+// fails) and RT4_RENDER_FAIL_STAGE=gather (its part of the gather fails instead); what they do: render_shards.
+struct ShardHooks {
+  bool rehearse;
+  int fail_rank;
+  bool fail_gather;
+};
+
+ShardHooks shard_hooks(bool rehearse) {
+  const char* fail_env = std::getenv("RT4_RENDER_FAIL_RANK");
+  const char* stage_env = std::getenv("RT4_RENDER_FAIL_STAGE");
+  return {rehearse, fail_env ? std::atoi(fail_env) : -1, stage_env && std::strcmp(stage_env, "gather") == 0};
+}
+
+struct ShardResult {
+  std::vector<unsigned char> image;  // the root's result on the host
+  unsigned long long count;          // intersections of all ranks
+  double ms;                         // the slowest rank's time
+};
+
 // One section on `gpus` devices: every rank renders its shard (job.render), one ncclGather of the
 // shards to rank 0, and the root's last step there (job.finish). For --gpus that is: pixel bands dealt round-robin
 // (rt4_band_plan), each rank's frames pipelined in one rt4_render_frames_device call into a padded
@@ -189,8 +209,12 @@ struct ShardJob {
 // (ncclCommAbort), so no rank waits forever in a collective its peer never joined. While the gather runs, every
 // rank also watches its communicator's asynchronous error (ncclCommGetAsyncError) and a shared abort flag.
 // Returns the root's result on the host (rank 0's), or exits with status 1 naming the failed rank(s).
-std::vector<unsigned char> render_shards(int gpus, const rt4_scene_desc* scene, const ShardJob& job, bool rehearse,
-                                         int fail_rank, bool fail_gather, unsigned long long* count_out, double* ms_out) {
+// rank_main below is, word for word, the function it was before this program was cut into steps:
+// its branch without --rehearse needs two GPUs to run, so only the way it receives rehearse, fail_rank and
+// fail_gather changed.
+ShardResult render_shards(int gpus, const rt4_scene_desc* scene, const ShardJob& job, const ShardHooks& hooks) {
+  const bool rehearse = hooks.rehearse, fail_gather = hooks.fail_gather;
+  const int fail_rank = hooks.fail_rank;
   std::vector<ncclComm_t> comms(static_cast<size_t>(gpus), nullptr);
   if (!rehearse) {
     std::vector<int> devs(static_cast<size_t>(gpus));
@@ -307,9 +331,7 @@ std::vector<unsigned char> render_shards(int gpus, const rt4_scene_desc* scene, 
     ms = std::max(ms, run.ms);  // the job's time: the slowest rank
   }
   if (!errors.empty()) die(job.flag, errors.c_str());
-  *count_out = count;
-  *ms_out = ms;
-  return image;
+  return {std::move(image), count, ms};
 }
 
 // The band plan of every rank (rt4_band_plan), shared by the two band-split jobs below.
@@ -324,9 +346,8 @@ struct BandPlans {
 };
 
 // --gpus: the colour frames of one section in pixel bands.
-std::vector<unsigned char> render_bands(int gpus, int band, const rt4_scene_desc* scene, const std::vector<rt4_uniforms>& us,
-                                        int32_t w, int32_t h, int32_t format, bool frame_by_frame, bool rehearse,
-                                        int fail_rank, bool fail_gather, unsigned long long* count_out, double* ms_out) {
+ShardResult render_bands(int gpus, int band, const rt4_scene_desc* scene, const std::vector<rt4_uniforms>& us, int32_t w,
+                         int32_t h, int32_t format, bool frame_by_frame, const ShardHooks& hooks) {
   const size_t px = static_cast<size_t>(rt4_frame_format_bytes(format));
   const BandPlans plan(gpus, band, w, h, "--gpus");
   std::vector<char> pipelined(static_cast<size_t>(gpus), 0);
@@ -357,7 +378,7 @@ std::vector<unsigned char> render_bands(int gpus, int band, const rt4_scene_desc
   job.finish = [&](rt4_context*, const void* gathered, void* image, hipStream_t stream, char* err, size_t errlen) {
     return rt4_bands_unpermute_device(gathered, image, w, h, gpus, band, plan.rows_max, format, stream, err, errlen);
   };
-  return render_shards(gpus, scene, job, rehearse, fail_rank, fail_gather, count_out, ms_out);
+  return render_shards(gpus, scene, job, hooks);
 }
 
 // --light-gpus: the light accumulator of one section. bands: the accumulator's pixels in the bands of --gpus, every rank
@@ -365,10 +386,8 @@ std::vector<unsigned char> render_bands(int gpus, int band, const rt4_scene_desc
 // every rank the whole image for its block of the frame numbers (rt4_frame_split; a rank without frames leaves its
 // shard empty), one rt4_light_merge_device of all ranks' accumulators into the root's empty one: as accurate as the
 // one-GPU accumulator, not bit-equal to it. us[n - 1] holds the uniforms of frame n.
-std::vector<unsigned char> render_light_shards(int gpus, bool split_bands, int band, const rt4_scene_desc* scene,
-                                               const std::vector<rt4_uniforms>& us, int32_t w, int32_t h, bool rehearse,
-                                               int fail_rank, bool fail_gather, unsigned long long* count_out,
-                                               double* ms_out) {
+ShardResult render_light_shards(int gpus, bool split_bands, int band, const rt4_scene_desc* scene,
+                                const std::vector<rt4_uniforms>& us, int32_t w, int32_t h, const ShardHooks& hooks) {
   const size_t px = sizeof(rt4_light_px);
   const int32_t n_frames = static_cast<int32_t>(us.size());
   ShardJob job;
@@ -392,7 +411,7 @@ std::vector<unsigned char> render_light_shards(int gpus, bool split_bands, int b
       return rt4_light_bands_unpermute_device(static_cast<const rt4_light_px*>(gathered), static_cast<rt4_light_px*>(image), w,
                                               h, gpus, band, plan.rows_max, stream, err, errlen);
     };
-    return render_shards(gpus, scene, job, rehearse, fail_rank, fail_gather, count_out, ms_out);
+    return render_shards(gpus, scene, job, hooks);
   }
   const rt4_region whole{0, 0, w, h, 0, 0};
   std::vector<int32_t> first(static_cast<size_t>(gpus)), count(static_cast<size_t>(gpus));
@@ -415,687 +434,750 @@ std::vector<unsigned char> render_light_shards(int gpus, bool split_bands, int b
     return rt4_light_merge_device(ctx, static_cast<rt4_light_px*>(image), w, static_cast<const rt4_light_px*>(gathered), w,
                                   static_cast<int64_t>(w) * h, gpus, w, h, stream, err, errlen);
   };
-  return render_shards(gpus, scene, job, rehearse, fail_rank, fail_gather, count_out, ms_out);
+  return render_shards(gpus, scene, job, hooks);
 }
 
-void write_raw(const std::string& path, const std::vector<unsigned char>& bytes) {  // --raw
-  std::FILE* f = std::fopen(path.c_str(), "wb");
-  if (!f) die("--raw", path.c_str());
-  const bool ok = std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
-  if (std::fclose(f) != 0 || !ok) die("--raw: write failed", path.c_str());
-}
-
-uint32_t keys_from(const char* s) {  // controls.cpp:98-113 key names
+uint32_t keys_from(const char* s) {  // controls.cpp:98-113 key names; other letters are ignored
+  static const char names[] = "WSDA ULEQ";
+  static const uint32_t bits[] = {RT4_KEY_FORWARD, RT4_KEY_BACK, RT4_KEY_RIGHT, RT4_KEY_LEFT, RT4_KEY_UP,
+                                  RT4_KEY_UP,      RT4_KEY_DOWN, RT4_KEY_W_POS, RT4_KEY_W_NEG};
   uint32_t k = 0;
-  for (; *s; ++s) switch (*s) {
-      case 'W': k |= RT4_KEY_FORWARD; break;
-      case 'S': k |= RT4_KEY_BACK; break;
-      case 'D': k |= RT4_KEY_RIGHT; break;
-      case 'A': k |= RT4_KEY_LEFT; break;
-      case ' ': case 'U': k |= RT4_KEY_UP; break;
-      case 'L': k |= RT4_KEY_DOWN; break;
-      case 'E': k |= RT4_KEY_W_POS; break;
-      case 'Q': k |= RT4_KEY_W_NEG; break;
-      default: break;
-    }
+  for (; *s; ++s) if (const char* at = std::strchr(names, *s)) k |= bits[at - names];
   return k;
 }
 
-}  // namespace
+// A params struct of the library with its defaults: defaults(rt4_denoise_params_default).
+template <class P> P defaults(void (*fill)(P*)) {
+  P p;
+  fill(&p);
+  return p;
+}
 
-int main(int argc, char** argv) {
-  // The frame loop's overlapped launches of small frames use up to 8 side streams (DESIGN.md §4.28): give the
-  // process 8 hardware queues unless the environment says otherwise (read when the HIP runtime starts).
-  setenv("GPU_MAX_HW_QUEUES", "8", 0);
+// The command line (parse_args). What may go together is refuse_conflicts' business.
+struct Options {
+  // what to render, from where, and where to write it
   std::string props_path = "properties.txt", scene_arg, out = "frame", fmt_name = "f32";
   int frames = 1, device = 0, width = 0, height = 0;
-  bool three = false, frame_by_frame = false;
-  int gpus = 0, band = 8;
+  int32_t format = RT4_FRAME_RGBA32F;  // from fmt_name (-f)
   uint32_t seed = 12345, keys = 0;
   float move_seconds = 0.0f;
-  std::string resume_path, checkpoint_path;
-  bool png = false, rehearse = false, raw = false;
-  int denoise_levels = 0;  // --denoise: 0 = off
-  int light_denoise_levels = -1;  // --light-denoise: -1 = off
-  bool reproject = false;
-  int window_scale = 0;  // --window: 0 = off, -1 = the properties' cell_size
-  bool window_nearest = false;
-  bool light = false, noise_map = false;  // --light, --noise-map
+  bool three = false, frame_by_frame = false, png = false, raw = false, reproject = false;
+  // --gpus and --light-gpus (the light path's own)
+  int gpus = 0, light_gpus = 0, band = 8;
+  bool rehearse = false, light_split_given = false;
+  std::string light_split = "frames";
+  // checkpoints: the colour path's; the light path's own, and the files of --light-pool
+  std::string resume_path, checkpoint_path, light_resume_path, light_checkpoint_path;
+  std::vector<std::string> light_pool;
+  // --denoise: 0 = off; --light-denoise: -1 = off; --window: 0 = off, -1 = the properties' cell_size
+  int denoise_levels = 0, light_denoise_levels = -1, window_scale = 0;
+  bool window_nearest = false, light = false, noise_map = false;
   float noise_threshold = 1.0f / 255.0f;  // --noise-threshold: one 8-bit step
   // --adaptive (needs --light): the loop of DESIGN.md §4.39 in place of -n uniform frames; -n is then the budget in
   // whole-frame equivalents. The defaults are the values of that section's study.
   bool adaptive = false, ad_given = false;
   int ad_warmup = 8, ad_pass = 4, ad_full_every = 4;  // --adaptive-warmup / --adaptive-pass / --adaptive-full-every
-  rt4_tile_select_params ad_select;                   // --adaptive-min-above / --adaptive-dilate; threshold: --noise-threshold
-  rt4_tile_select_params_default(&ad_select);
-  // --light-resume / --light-checkpoint / --light-gpus / --light-pool: the light path's own restart,
-  // multi-GPU and pooling flags; --resume, --checkpoint and --gpus stay the colour path's
-  std::string light_resume_path, light_checkpoint_path, light_split = "frames";
-  bool light_split_given = false;
-  int light_gpus = 0;
-  std::vector<std::string> light_pool;
+  // --adaptive-min-above / --adaptive-dilate; threshold: --noise-threshold
+  rt4_tile_select_params ad_select = defaults(rt4_tile_select_params_default);
+
+  bool pool() const { return !light_pool.empty(); }
+  bool moving() const { return keys && move_seconds > 0.0f; }
+  bool checkpoints() const { return !resume_path.empty() || !checkpoint_path.empty(); }
+  int32_t px() const { return rt4_frame_format_bytes(format); }  // bytes per pixel of a frame
+  // One section and a resting camera (progressive accumulation): the frames go to the library in one
+  // rt4_render_frames_device call (pipelined through one pixel queue; the same final image).
+  bool pipelined() const { return !three && !moving() && !frame_by_frame && !reproject && !light; }
+};
+
+// The number after a flag that may also stand alone: the next argument if it starts with a digit, else alone.
+int optional_number(int argc, char** argv, int& i, int alone) {
+  return i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' ? std::atoi(argv[++i]) : alone;
+}
+
+Options parse_args(int argc, char** argv) {
+  Options o;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* {
       if (i + 1 >= argc) die("missing value for", a.c_str());
       return argv[++i];
     };
-    if (a == "-p") props_path = next();
-    else if (a == "-s") scene_arg = next();
-    else if (a == "-n") frames = std::atoi(next());
-    else if (a == "-3") three = true;
-    else if (a == "-W") width = std::atoi(next());
-    else if (a == "-H") height = std::atoi(next());
-    else if (a == "-f") fmt_name = next();
-    else if (a == "--seed") seed = static_cast<uint32_t>(std::strtoul(next(), nullptr, 0));
-    else if (a == "-o") out = next();
-    else if (a == "-d") device = std::atoi(next());
-    else if (a == "--keys") keys = keys_from(next());
-    else if (a == "--frame-by-frame") frame_by_frame = true;
-    else if (a == "--move-seconds") move_seconds = static_cast<float>(std::atof(next()));
-    else if (a == "--gpus") gpus = std::atoi(next());
-    else if (a == "--band") band = std::atoi(next());
-    else if (a == "--resume") resume_path = next();
-    else if (a == "--checkpoint") checkpoint_path = next();
-    else if (a == "--png") png = true;
-    else if (a == "--raw") raw = true;
-    else if (a == "--rehearse") rehearse = true;
-    else if (a == "--reproject") reproject = true;
-    else if (a == "--light") light = true;
-    else if (a == "--noise-map") noise_map = true;
-    else if (a == "--noise-threshold") noise_threshold = static_cast<float>(std::atof(next()));
-    else if (a == "--light-resume") light_resume_path = next();
-    else if (a == "--light-checkpoint") light_checkpoint_path = next();
-    else if (a == "--light-gpus") light_gpus = std::atoi(next());
-    else if (a == "--light-split") light_split = next(), light_split_given = true;
+    if (a == "-p") o.props_path = next();
+    else if (a == "-s") o.scene_arg = next();
+    else if (a == "-n") o.frames = std::atoi(next());
+    else if (a == "-3") o.three = true;
+    else if (a == "-W") o.width = std::atoi(next());
+    else if (a == "-H") o.height = std::atoi(next());
+    else if (a == "-f") o.fmt_name = next();
+    else if (a == "--seed") o.seed = static_cast<uint32_t>(std::strtoul(next(), nullptr, 0));
+    else if (a == "-o") o.out = next();
+    else if (a == "-d") o.device = std::atoi(next());
+    else if (a == "--keys") o.keys = keys_from(next());
+    else if (a == "--frame-by-frame") o.frame_by_frame = true;
+    else if (a == "--move-seconds") o.move_seconds = static_cast<float>(std::atof(next()));
+    else if (a == "--gpus") o.gpus = std::atoi(next());
+    else if (a == "--band") o.band = std::atoi(next());
+    else if (a == "--resume") o.resume_path = next();
+    else if (a == "--checkpoint") o.checkpoint_path = next();
+    else if (a == "--png") o.png = true;
+    else if (a == "--raw") o.raw = true;
+    else if (a == "--rehearse") o.rehearse = true;
+    else if (a == "--reproject") o.reproject = true;
+    else if (a == "--light") o.light = true;
+    else if (a == "--noise-map") o.noise_map = true;
+    else if (a == "--noise-threshold") o.noise_threshold = static_cast<float>(std::atof(next()));
+    else if (a == "--light-resume") o.light_resume_path = next();
+    else if (a == "--light-checkpoint") o.light_checkpoint_path = next();
+    else if (a == "--light-gpus") o.light_gpus = std::atoi(next());
+    else if (a == "--light-split") o.light_split = next(), o.light_split_given = true;
     else if (a == "--light-pool") {  // every following argument up to the next flag
-      while (i + 1 < argc && argv[i + 1][0] != '-') light_pool.push_back(argv[++i]);
-      if (light_pool.size() < 2) die("--light-pool", "needs two or more light checkpoints");
-      light = true;
-    }
-    else if (a == "--adaptive") adaptive = true;
-    else if (a == "--adaptive-warmup") ad_warmup = std::atoi(next()), ad_given = true;
-    else if (a == "--adaptive-pass") ad_pass = std::atoi(next()), ad_given = true;
-    else if (a == "--adaptive-full-every") ad_full_every = std::atoi(next()), ad_given = true;
-    else if (a == "--adaptive-min-above") ad_select.min_above = std::atoi(next()), ad_given = true;
-    else if (a == "--adaptive-dilate") ad_select.dilate = std::atoi(next()), ad_given = true;
-    else if (a == "--window-nearest") {
-      window_nearest = true;
-      if (window_scale == 0) window_scale = -1;
-    }
+      while (i + 1 < argc && argv[i + 1][0] != '-') o.light_pool.push_back(argv[++i]);
+      if (o.light_pool.size() < 2) die("--light-pool", "needs two or more light checkpoints");
+      o.light = true;
+    } else if (a == "--adaptive") o.adaptive = true;
+    else if (a == "--adaptive-warmup") o.ad_warmup = std::atoi(next()), o.ad_given = true;
+    else if (a == "--adaptive-pass") o.ad_pass = std::atoi(next()), o.ad_given = true;
+    else if (a == "--adaptive-full-every") o.ad_full_every = std::atoi(next()), o.ad_given = true;
+    else if (a == "--adaptive-min-above") o.ad_select.min_above = std::atoi(next()), o.ad_given = true;
+    else if (a == "--adaptive-dilate") o.ad_select.dilate = std::atoi(next()), o.ad_given = true;
+    else if (a == "--window-nearest") o.window_nearest = true, o.window_scale = o.window_scale ? o.window_scale : -1;
     else if (a == "--window") {
-      window_scale = -1;
-      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {
-        window_scale = std::atoi(argv[++i]);
-        if (window_scale < 1 || window_scale > RT4_UPSCALE_MAX_SCALE) die("--window", "SCALE must be 1..64");
-      }
-    }
-    else if (a == "--denoise") {
-      rt4_denoise_params dp;
-      rt4_denoise_params_default(&dp);
-      denoise_levels = dp.levels;
-      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise_levels = std::atoi(argv[++i]);
-      if (denoise_levels < 1 || denoise_levels > RT4_DENOISE_MAX_LEVELS) die("--denoise", "levels must be 1..6");
-    }
-    else if (a == "--light-denoise") {
-      rt4_light_denoise_params lp;
-      rt4_light_denoise_params_default(&lp);
-      light_denoise_levels = lp.levels;
-      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') light_denoise_levels = std::atoi(argv[++i]);
-      if (light_denoise_levels < 0 || light_denoise_levels > RT4_LIGHT_DENOISE_MAX_LEVELS)
+      o.window_scale = optional_number(argc, argv, i, -1);
+      if (o.window_scale != -1 && (o.window_scale < 1 || o.window_scale > RT4_UPSCALE_MAX_SCALE))
+        die("--window", "SCALE must be 1..64");
+    } else if (a == "--denoise") {
+      o.denoise_levels = optional_number(argc, argv, i, defaults(rt4_denoise_params_default).levels);
+      if (o.denoise_levels < 1 || o.denoise_levels > RT4_DENOISE_MAX_LEVELS) die("--denoise", "levels must be 1..6");
+    } else if (a == "--light-denoise") {
+      o.light_denoise_levels = optional_number(argc, argv, i, defaults(rt4_light_denoise_params_default).levels);
+      if (o.light_denoise_levels < 0 || o.light_denoise_levels > RT4_LIGHT_DENOISE_MAX_LEVELS)
         die("--light-denoise", "levels must be 0..6");
-    }
-    else die("unknown argument", a.c_str());
+    } else die("unknown argument", a.c_str());
   }
-  if (reproject && gpus > 0) die("--reproject", "not with --gpus: the temporal image lives on one GPU");
-  if (reproject && (!resume_path.empty() || !checkpoint_path.empty()))
+  o.format = o.fmt_name == "f16" ? RT4_FRAME_RGBA16F : o.fmt_name == "rgba8" ? RT4_FRAME_RGBA8 : RT4_FRAME_RGBA32F;
+  if (o.pool()) o.frames = 0;  // nothing is rendered
+  return o;
+}
+
+// Every combination of flags that is refused whatever the files hold, in one place: the first check that fails is the
+// one reported, so the order below is part of the program's behaviour (tests/test_render_cli_refusals.py pins it).
+// What depends on a file's contents (a checkpoint's seed, key, size, pooled flag; the 2^32 frame bound) is refused by
+// load_inputs, and a missing device by need_devices, after this.
+void refuse_conflicts(const Options& o) {
+  if (o.reproject && o.gpus > 0) die("--reproject", "not with --gpus: the temporal image lives on one GPU");
+  if (o.reproject && o.checkpoints())
     die("--reproject", "not with --resume / --checkpoint: a checkpoint holds no per-pixel history");
-  if (reproject && frame_by_frame) die("--reproject", "not with --frame-by-frame: every temporal frame is a launch of its own");
-  if (light && reproject) die("--light", "not with --reproject: the temporal history is a colour average");
-  if (light && (!resume_path.empty() || !checkpoint_path.empty()))
+  if (o.reproject && o.frame_by_frame)
+    die("--reproject", "not with --frame-by-frame: every temporal frame is a launch of its own");
+  if (o.light && o.reproject) die("--light", "not with --reproject: the temporal history is a colour average");
+  if (o.light && o.checkpoints())
     die("--light", "not with --resume / --checkpoint: a checkpoint holds colours, not a light accumulator "
                    "(--light-resume / --light-checkpoint save and continue a light accumulator)");
-  if (light && gpus > 0)
+  if (o.light && o.gpus > 0)
     die("--light", "not with --gpus: that gathers colour frames (--light-gpus N runs a light accumulator on N GPUs)");
-  const bool pool = !light_pool.empty();
-  if ((!light_resume_path.empty() || !light_checkpoint_path.empty() || light_gpus != 0 || light_split_given) && !light)
+  const bool light_files = !o.light_resume_path.empty() || !o.light_checkpoint_path.empty();
+  if ((light_files || o.light_gpus != 0 || o.light_split_given) && !o.light)
     die("--light-resume / --light-checkpoint / --light-gpus / --light-split", "need --light");
-  if (light_split_given && light_gpus == 0) die("--light-split", "needs --light-gpus");
-  if (light_split != "frames" && light_split != "bands") die("--light-split", "frames or bands");
-  if (light_gpus != 0 && (light_gpus < 1 || light_gpus > RT4_LIGHT_MERGE_MAX))
+  if (o.light_split_given && o.light_gpus == 0) die("--light-split", "needs --light-gpus");
+  if (o.light_split != "frames" && o.light_split != "bands") die("--light-split", "frames or bands");
+  if (o.light_gpus != 0 && (o.light_gpus < 1 || o.light_gpus > RT4_LIGHT_MERGE_MAX))
     die("--light-gpus", "N must be 1..16 (RT4_LIGHT_MERGE_MAX: one merge takes that many accumulators)");
-  if (light_gpus > 0 && adaptive) die("--light-gpus", "not with --adaptive: the tile selection runs on one GPU");
-  if (light_gpus > 0 && !light_resume_path.empty()) die("--light-gpus", "not with --light-resume: resume on one GPU");
-  if (!light_resume_path.empty() && adaptive)
+  if (o.light_gpus > 0 && o.adaptive) die("--light-gpus", "not with --adaptive: the tile selection runs on one GPU");
+  if (o.light_gpus > 0 && !o.light_resume_path.empty()) die("--light-gpus", "not with --light-resume: resume on one GPU");
+  if (!o.light_resume_path.empty() && o.adaptive)
     die("--light-resume", "not with --adaptive: a light checkpoint does not hold the adaptive loop's pass state");
-  if (pool && (adaptive || light_gpus > 0 || !light_resume_path.empty() || three || denoise_levels > 0 ||
-               light_denoise_levels >= 0 || window_scale != 0 || reproject))
+  if (o.pool() && (o.adaptive || o.light_gpus > 0 || !o.light_resume_path.empty() || o.three || o.denoise_levels > 0 ||
+                   o.light_denoise_levels >= 0 || o.window_scale != 0 || o.reproject))
     die("--light-pool", "renders nothing: only with -o, --png, --raw, --noise-map, --noise-threshold, --light-checkpoint");
-  if (light && frame_by_frame) die("--light", "not with --frame-by-frame: the frames go through rt4_render_light_device");
-  if (light && keys && move_seconds > 0.0f) die("--light", "needs a resting camera: the accumulator averages one view");
-  if ((noise_map || noise_threshold != 1.0f / 255.0f) && !light) die("--noise-map / --noise-threshold", "need --light");
-  if ((adaptive || ad_given) && !light) die("--adaptive", "needs --light: it samples by the light accumulator's standard error");
-  if (ad_given && !adaptive) die("--adaptive-*", "need --adaptive");
-  if (adaptive && (ad_warmup < 0 || ad_pass < 1 || ad_full_every < 0 || ad_select.min_above < 1 || ad_select.min_above > 64 ||
-                   ad_select.dilate < 0 || ad_select.dilate > RT4_SELECT_MAX_DILATE || noise_threshold != noise_threshold))
+  if (o.light && o.frame_by_frame) die("--light", "not with --frame-by-frame: the frames go through rt4_render_light_device");
+  if (o.light && o.moving()) die("--light", "needs a resting camera: the accumulator averages one view");
+  if ((o.noise_map || o.noise_threshold != 1.0f / 255.0f) && !o.light) die("--noise-map / --noise-threshold", "need --light");
+  if ((o.adaptive || o.ad_given) && !o.light)
+    die("--adaptive", "needs --light: it samples by the light accumulator's standard error");
+  if (o.ad_given && !o.adaptive) die("--adaptive-*", "need --adaptive");
+  if (o.adaptive && (o.ad_warmup < 0 || o.ad_pass < 1 || o.ad_full_every < 0 || o.ad_select.min_above < 1 ||
+                     o.ad_select.min_above > 64 || o.ad_select.dilate < 0 || o.ad_select.dilate > RT4_SELECT_MAX_DILATE ||
+                     o.noise_threshold != o.noise_threshold))
     die("--adaptive", "warmup >= 0, pass >= 1, full-every >= 0, min-above 1..64, dilate 0..2, a threshold that is a number");
-  if (light_denoise_levels >= 0 && !light) die("--light-denoise", "needs --light: it filters the light accumulator");
-  if (light_denoise_levels >= 0 && denoise_levels > 0)
+  if (o.light_denoise_levels >= 0 && !o.light) die("--light-denoise", "needs --light: it filters the light accumulator");
+  if (o.light_denoise_levels >= 0 && o.denoise_levels > 0)
     die("--light-denoise", "not with --denoise: one filtered frame per image");
-  const int32_t format = fmt_name == "f16" ? RT4_FRAME_RGBA16F : fmt_name == "rgba8" ? RT4_FRAME_RGBA8 : RT4_FRAME_RGBA32F;
-  char err[1024] = {0};
+  // These once ran between and after the loads. Whenever a checkpoint loader could have run ahead of one of them, a
+  // check above has already refused the command line, so only a command line that is refused here and also names a
+  // properties or scene file that does not load hears another message than it used to: this one.
+  if (o.checkpoints() && (o.three || o.gpus > 0)) die("--resume/--checkpoint", "need one section on one GPU");
+  if (light_files && o.three) die("--light-resume / --light-checkpoint", "need one section");
+  // as --gpus: one section (the camera rests in every --light run)
+  if (o.light_gpus > 0 && o.three) die("--light-gpus", "needs one section");
+  if (o.light_gpus > 0 && (o.frames < 1 || o.band < 1)) die("--light-gpus", "frames and band must be >= 1");
+  if (o.gpus > 0 && o.denoise_levels > 0) die("--denoise", "not with --gpus: the frame is not filtered after the gather");
+  if (o.gpus > 0 && o.window_scale != 0) die("--window", "not with --gpus: the frame is not upscaled after the gather");
+  // pixel bands over GPUs 0..gpus-1, one RCCL gather (one section, resting camera)
+  if (o.gpus > 0 && (o.three || o.moving())) die("--gpus", "needs one section and a resting camera");
+  if (o.gpus > 0 && (o.frames < 1 || o.band < 1)) die("--gpus", "frames and band must be >= 1");
+}
+
+// --gpus / --light-gpus without --rehearse (a rehearsal puts every rank on device 0 and reports a missing device per rank)
+void need_devices(const char* flag, int n) {
+  int ndev = 0;
+  HIP_CHECK(hipGetDeviceCount(&ndev));
+  if (n > ndev) die(flag, ("only " + std::to_string(ndev) + " HIP devices").c_str());
+}
+
+// One image of the run: the main section (window.main cells, or -W/-H) or, with -3, YWZ / YXW (window.additional).
+struct Section {
+  int id;
+  const char *name, *window;  // "yxz", and whose cells and cell_size in the properties: "main" / "additional"
+  int32_t w = 0, h = 0;
+  rt4_uniforms base = {};           // from the properties, at w x h
+  int32_t win_scale = 0;            // --window: this section's scale
+  void* d_frame = nullptr;          // the image, in the run's frame format
+  rt4_light_px* d_light = nullptr;  // --light: the accumulator
+  rt4_temporal* temporal = nullptr;  // --reproject
+  rt4_uniforms last_u = {};         // the last frame's uniforms: the camera pose the images show
+
+  size_t pixels() const { return static_cast<size_t>(w) * h; }
+  size_t frame_bytes(int32_t px) const { return pixels() * static_cast<size_t>(px); }
+  rt4_region region() const { return rt4_region{0, 0, w, h, 0, 0}; }
+  float tone() const { return base.light_to_color_conversion_coefficient; }  // of the tone curve (resolve, filter, noise)
+};
+
+char err[1024] = {0};  // RT4_CHECK's message buffer in the steps below (the main thread's)
+
+// What the steps hand on: everything the run reads before it touches a GPU (load_inputs), and the one-GPU run's
+// device state besides the sections' buffers (open_render).
+struct Run {
   rt4_properties* props = nullptr;
-  RT4_CHECK(rt4_properties_load(props_path.c_str(), &props, err, sizeof err));
-
-  // scene: -s builtin name or .frag path; else the properties' shader_filename (main.cpp:26)
-  rt4_scene_desc* scene = static_cast<rt4_scene_desc*>(std::calloc(1, sizeof(rt4_scene_desc)));
-  if (scene_arg.empty()) {
-    char buf[4096];
-    size_t need = 0;
-    RT4_CHECK(rt4_properties_get_string(props, "shader_filename", buf, sizeof buf, &need, err, sizeof err));
-    scene_arg = buf;
-  }
-  if (scene_arg.size() > 5 && scene_arg.compare(scene_arg.size() - 5, 5, ".frag") == 0)
-    RT4_CHECK(rt4_scene_load_frag(scene_arg.c_str(), scene, err, sizeof err));
-  else
-    RT4_CHECK(rt4_scene_builtin(scene_arg.c_str(), scene, err, sizeof err));
-
-  // images: the main section (window.main cells, or -W/-H) and, with -3, YWZ / YXW (window.additional)
-  const int n_img = three ? 3 : 1;
-  int32_t cw[3], ch[3];
-  if (width > 0 && height > 0) {
-    cw[0] = width;
-    ch[0] = height;
-  } else {
-    RT4_CHECK(rt4_window_cells(props, "main", &cw[0], &ch[0], err, sizeof err));
-  }
-  if (three) {
-    RT4_CHECK(rt4_window_cells(props, "additional", &cw[1], &ch[1], err, sizeof err));
-    cw[2] = cw[1];
-    ch[2] = ch[1];
-  }
-  const int sections[3] = {RT4_SECTION_YXZ, RT4_SECTION_YWZ, RT4_SECTION_YXW};
-  rt4_uniforms base[3];
-  for (int q = 0; q < n_img; q++)
-    RT4_CHECK(rt4_uniforms_from_properties(props, cw[q], ch[q], sections[q], &base[q], nullptr, err, sizeof err));
+  rt4_scene_desc* scene = nullptr;
+  std::vector<Section> sections;
   rt4_camera cam;
-  RT4_CHECK(rt4_camera_init(props, &cam, err, sizeof err));
-
   // the run's key, checked on --resume and recorded by --checkpoint: the first frame's uniforms (seed and
   // part aside they are every resting frame's)
   uint32_t run_key = 0;
-  {
-    rt4_camera c0 = cam;
-    rt4_uniforms u0;
-    RT4_CHECK(rt4_camera_frame_uniforms(&c0, &base[0], sections[0], 0, &u0));
-    run_key = rt4_accum_key(scene, &u0);
-  }
-  if ((!resume_path.empty() || !checkpoint_path.empty()) && (three || gpus > 0))
-    die("--resume/--checkpoint", "need one section on one GPU");
-  // frames already blended into the accumulator (a resumed run continues at frame frames_done + 1)
-  int64_t frames_done = 0;
-  std::vector<unsigned char> resumed;
-  if (!resume_path.empty()) {
-    uint32_t ck_seed = 0;
-    resumed.resize(static_cast<size_t>(cw[0]) * ch[0] * rt4_frame_format_bytes(format));
-    RT4_CHECK(rt4_accum_load(resume_path.c_str(), resumed.data(), format, cw[0], ch[0], cw[0], &frames_done, &ck_seed, err,
-                             sizeof err));
-    if (ck_seed != seed) die("--resume", "the checkpoint was made with another --seed");
-    // the checkpoint's run key (scene, samples, bounces, resolution, camera ...): a checkpoint of
-    // another run would be blended in silently
-    uint32_t ck_key = 0;
-    RT4_CHECK(rt4_accum_key_of(resume_path.c_str(), &ck_key, err, sizeof err));
-    if (ck_key != 0u && ck_key != run_key)
-      die("--resume", "the checkpoint was made with another scene, properties or camera");
-    cam.frame_number = static_cast<uint32_t>(frames_done + 1);
-  }
-  // --light-resume: the accumulator the run continues (frames frames_done + 1 ...); --light-pool: the accumulators of
-  // independent runs, merged once there is a context. Both are refused rather than mixed with another run's frames.
-  if ((!light_resume_path.empty() || !light_checkpoint_path.empty()) && three)
-    die("--light-resume / --light-checkpoint", "need one section");
+  int64_t frames_done = 0;  // frames already blended into the accumulator (a resumed run continues at frame frames_done + 1)
+  std::vector<unsigned char> resumed;     // --resume: the loaded frame
   std::vector<rt4_light_px> light_start;  // --light-resume: the loaded accumulator; --light-pool: every file's, in order
-  uint32_t pool_seed = 0, pool_key = 0;
+  uint32_t pool_seed = 0, pool_key = 0;   // --light-pool: the first file's
   int64_t pool_issued = 0;
-  if (!light_resume_path.empty()) {
-    uint32_t ck_seed = 0, ck_key = 0, ck_flags = 0;
-    int32_t ck_w = 0, ck_h = 0;
-    RT4_CHECK(rt4_light_info(light_resume_path.c_str(), &ck_w, &ck_h, nullptr, &ck_seed, &ck_key, &ck_flags, err, sizeof err));
-    if (ck_flags & RT4_LIGHT_POOLED) die("--light-resume", "the checkpoint pools runs of several seeds: it cannot be resumed");
-    if (ck_w != cw[0] || ck_h != ch[0])
-      die("--light-resume", ("the checkpoint holds a " + std::to_string(ck_w) + "x" + std::to_string(ck_h) + " accumulator, not " +
-                             std::to_string(cw[0]) + "x" + std::to_string(ch[0])).c_str());
-    if (ck_seed != seed) die("--light-resume", "the checkpoint was made with another --seed");
-    if (ck_key != 0u && ck_key != run_key)
-      die("--light-resume", "the checkpoint was made with another scene, properties or camera");
-    light_start.resize(static_cast<size_t>(cw[0]) * ch[0]);
-    RT4_CHECK(rt4_light_load(light_resume_path.c_str(), light_start.data(), cw[0], ch[0], cw[0], &frames_done, nullptr, nullptr,
-                             nullptr, err, sizeof err));
-    if (frames_done + frames > 0xFFFFFFFFll) die("--light-resume", "frame numbers beyond 2^32 - 1");
-    cam.frame_number = static_cast<uint32_t>(frames_done + 1);
-  }
-  if (pool) {
-    std::vector<uint32_t> seeds;
-    for (size_t s = 0; s < light_pool.size(); s++) {
-      int32_t fw = 0, fh = 0;
-      int64_t issued = 0;
-      uint32_t ck_seed = 0, ck_key = 0;
-      RT4_CHECK(rt4_light_info(light_pool[s].c_str(), &fw, &fh, &issued, &ck_seed, &ck_key, nullptr, err, sizeof err));
-      if (s == 0) {
-        cw[0] = fw, ch[0] = fh, pool_seed = ck_seed, pool_key = ck_key, pool_issued = issued;
-        light_start.resize(light_pool.size() * static_cast<size_t>(fw) * fh);
-      }
-      if (fw != cw[0] || fh != ch[0]) die("--light-pool: another image size than the first file's", light_pool[s].c_str());
-      if (ck_key != pool_key) die("--light-pool: another scene, properties or camera than the first file's", light_pool[s].c_str());
-      if (std::find(seeds.begin(), seeds.end(), ck_seed) != seeds.end())
-        die("--light-pool: the same --seed as an earlier file, the same frames would count twice", light_pool[s].c_str());
-      seeds.push_back(ck_seed);
-      RT4_CHECK(rt4_light_load(light_pool[s].c_str(), light_start.data() + s * static_cast<size_t>(fw) * fh, fw, fh, fw, nullptr,
-                               nullptr, nullptr, nullptr, err, sizeof err));
-    }
-    frames = 0;  // nothing is rendered
-  }
-  if (light_gpus > 0) {  // as --gpus: one section (the camera rests in every --light run)
-    if (three) die("--light-gpus", "needs one section");
-    if (frames < 1 || band < 1) die("--light-gpus", "frames and band must be >= 1");
-    if (!rehearse) {
-      int ndev = 0;
-      HIP_CHECK(hipGetDeviceCount(&ndev));
-      if (light_gpus > ndev) die("--light-gpus", ("only " + std::to_string(ndev) + " HIP devices").c_str());
-    }
-  }
-
-  if (gpus > 0 && denoise_levels > 0) die("--denoise", "not with --gpus: the frame is not filtered after the gather");
-  if (gpus > 0 && window_scale != 0) die("--window", "not with --gpus: the frame is not upscaled after the gather");
-  int32_t win_scale[3] = {window_scale, window_scale, window_scale};  // per section
-  if (window_scale < 0) {
-    RT4_CHECK(rt4_properties_get_int(props, "window.main.cell_size", &win_scale[0], err, sizeof err));
-    if (three) RT4_CHECK(rt4_properties_get_int(props, "window.additional.cell_size", &win_scale[1], err, sizeof err));
-    win_scale[2] = win_scale[1];
-  }
-  if (gpus > 0) {  // pixel bands over GPUs 0..gpus-1, one RCCL gather (one section, resting camera)
-    if (three || (keys && move_seconds > 0.0f)) die("--gpus", "needs one section and a resting camera");
-    if (frames < 1 || band < 1) die("--gpus", "frames and band must be >= 1");
-    if (!rehearse) {  // a rehearsal puts every rank on device 0 and reports a missing device per rank
-      int ndev = 0;
-      HIP_CHECK(hipGetDeviceCount(&ndev));
-      if (gpus > ndev) die("--gpus", ("only " + std::to_string(ndev) + " HIP devices").c_str());
-    }
-    const char* fail_env = std::getenv("RT4_RENDER_FAIL_RANK");  // test hook: this rank's set-up fails,
-    const int fail_rank = fail_env ? std::atoi(fail_env) : -1;
-    const char* stage_env = std::getenv("RT4_RENDER_FAIL_STAGE");  // or with "gather" its part of the gather
-    const bool fail_gather = stage_env && std::strcmp(stage_env, "gather") == 0;
-    std::vector<rt4_uniforms> us;
-    for (int n = 1; n <= frames; n++) {
-      rt4_uniforms u;
-      RT4_CHECK(rt4_camera_frame_uniforms(&cam, &base[0], sections[0],
-                                          static_cast<int32_t>(seed ^ (static_cast<uint32_t>(n) * 0x9E3779B9u)), &u));
-      us.push_back(u);
-    }
-    unsigned long long count = 0;
-    double ms = 0.0;
-    const std::vector<unsigned char> img =
-        render_bands(gpus, band, scene, us, cw[0], ch[0], format, frame_by_frame, rehearse, fail_rank, fail_gather, &count,
-                     &ms);
-    const std::string path = out + (png ? "_yxz.png" : "_yxz.ppm");
-    RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(path.c_str(), img.data(), format, cw[0], ch[0], cw[0], err, sizeof err));
-    if (raw) write_raw(out + "_yxz.raw", img);
-    std::printf("wrote %s (%d x %d)\n", path.c_str(), cw[0], ch[0]);
-    std::printf("gpus %d, frames %d, images 1, intersections %llu, %.3f ms/frame, %.3e intersections/s\n", gpus,
-                frames, count, ms / frames, static_cast<double>(count) / (ms * 1e-3));
-    rt4_properties_free(props);
-    std::free(scene);
-    return 0;
-  }
 
   rt4_context* ctx = nullptr;
-  RT4_CHECK(rt4_context_create(device, RT4_FLAG_SAMPLER_LUT, &ctx, err, sizeof err));
-  RT4_CHECK(rt4_context_set_scene(ctx, scene, err, sizeof err));
-  const int32_t px = rt4_frame_format_bytes(format);
-  void* d_frame[3] = {nullptr, nullptr, nullptr};
-  for (int q = 0; q < n_img; q++) {
-    HIP_CHECK(hipMalloc(&d_frame[q], static_cast<size_t>(cw[q]) * ch[q] * px));
-    HIP_CHECK(hipMemset(d_frame[q], 0, static_cast<size_t>(cw[q]) * ch[q] * px));  // cleared RenderTexture
-  }
-  if (!resumed.empty()) HIP_CHECK(hipMemcpy(d_frame[0], resumed.data(), resumed.size(), hipMemcpyHostToDevice));
   unsigned long long* d_count = nullptr;
-  HIP_CHECK(hipMalloc(&d_count, sizeof *d_count));
-  HIP_CHECK(hipMemset(d_count, 0, sizeof *d_count));
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
+  hipEvent_t e0, e1;             // around render_frames
+  std::vector<rt4_uniforms> us;  // the pipelined run's frames (pipelined_frames)
+  int64_t light_issued = 0;  // the last progressive frame number folded into the light accumulator, for --light-checkpoint
+  double shards_ms = -1.0;   // --light-gpus: the slowest rank's time, in place of the events'
+  unsigned long long shards_count = 0, count = 0;  // intersections: the ranks'; the run's (render_frames)
+  float ms = 0.0f;                                 // render_frames: the time between its two event records
+};
 
-  // One section and a resting camera (progressive accumulation): the frames go to the library in one
-  // rt4_render_frames_device call (pipelined through one pixel queue; the same final image).
-  const bool pipelined = n_img == 1 && !(keys && move_seconds > 0.0f) && !frame_by_frame && !reproject && !light;
-  rt4_temporal* temporal[3] = {nullptr, nullptr, nullptr};  // --reproject: one per section
-  for (int q = 0; q < n_img && reproject; q++)
-    RT4_CHECK(rt4_temporal_create(ctx, cw[q], ch[q], format, &temporal[q], err, sizeof err));
-  std::vector<rt4_uniforms> us;
-  if (pipelined) {
-    // the frame-colour scratch only when frames are actually pipelined (>= 2 frames, a scene that does
-    // not run frame by frame), and only for the frames of one chunk
-    if (frames >= 2 && rt4_context_frames_per_launch(ctx, cw[0], ch[0]) > 1)
-      RT4_CHECK(rt4_context_reserve_frames(ctx, cw[0], ch[0], err, sizeof err));
-    for (int n = 1; n <= frames; n++) {
-      rt4_uniforms u;
-      const uint32_t fn = static_cast<uint32_t>(frames_done + n);
-      RT4_CHECK(rt4_camera_frame_uniforms(&cam, &base[0], sections[0], static_cast<int32_t>(seed ^ (fn * 0x9E3779B9u)), &u));
-      us.push_back(u);
-    }
-  }
-  rt4_uniforms last_u[3];  // the last frame's uniforms of every section: the camera pose the images show
-  if (pipelined && !us.empty()) last_u[0] = us.back();
-  static const char* names[3] = {"yxz", "ywz", "yxw"};
-  rt4_light_px* d_light[3] = {nullptr, nullptr, nullptr};  // --light: one accumulator per section
-  for (int q = 0; q < n_img && light; q++) {
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_light[q]), static_cast<size_t>(cw[q]) * ch[q] * sizeof(rt4_light_px)));
-    HIP_CHECK(hipMemset(d_light[q], 0, static_cast<size_t>(cw[q]) * ch[q] * sizeof(rt4_light_px)));  // empty
-  }
-  const size_t light_bytes0 = static_cast<size_t>(cw[0]) * ch[0] * sizeof(rt4_light_px);
-  if (!light_resume_path.empty()) HIP_CHECK(hipMemcpy(d_light[0], light_start.data(), light_bytes0, hipMemcpyHostToDevice));
-  if (pool) {
-    // the files merged in order into an empty accumulator, RT4_LIGHT_MERGE_MAX of them per call
-    std::vector<rt4_light_px> merged(static_cast<size_t>(cw[0]) * ch[0]);
-    std::memset(merged.data(), 0, light_bytes0);
-    const int64_t plane = static_cast<int64_t>(cw[0]) * ch[0];
-    for (size_t s0 = 0; s0 < light_pool.size(); s0 += RT4_LIGHT_MERGE_MAX)
-      RT4_CHECK(rt4_light_merge_host(ctx, merged.data(), cw[0], light_start.data() + s0 * static_cast<size_t>(plane), cw[0], plane,
-                                     static_cast<int32_t>(std::min<size_t>(RT4_LIGHT_MERGE_MAX, light_pool.size() - s0)), cw[0],
-                                     ch[0], err, sizeof err));
-    HIP_CHECK(hipMemcpy(d_light[0], merged.data(), light_bytes0, hipMemcpyHostToDevice));
-    RT4_CHECK(rt4_light_resolve_device(ctx, d_light[0], cw[0], base[0].light_to_color_conversion_coefficient, d_frame[0], format,
-                                       cw[0], cw[0], ch[0], nullptr, err, sizeof err));
-  }
-  // the last progressive frame number folded into the light accumulator: what --light-checkpoint records
-  int64_t light_issued = pool ? pool_issued : frames_done + frames;
-  double shards_ms = -1.0;  // --light-gpus: the slowest rank's time, in place of the events' below
-  unsigned long long shards_count = 0;
-  HIP_CHECK(hipEventRecord(e0, nullptr));
-  if (light && frames >= 1) {
-    // every section's frames in one rt4_render_light_device call (frame n of every section has the same seed, as in
-    // the loop below), then the image: the accumulator resolved into the section's frame
-    const uint32_t frame_number = cam.frame_number;
-    for (int q = 0; q < n_img; q++) {
-      std::vector<rt4_uniforms> lus(static_cast<size_t>(frames));
-      cam.frame_number = frame_number;
-      for (int n = 1; n <= frames; n++)  // frames_done: the frames a --light-resume checkpoint already holds
-        RT4_CHECK(rt4_camera_frame_uniforms(&cam, &base[q], sections[q],
-                                            static_cast<int32_t>(seed ^ (static_cast<uint32_t>(frames_done + n) * 0x9E3779B9u)),
-                                            &lus[static_cast<size_t>(n - 1)]));
-      last_u[q] = lus.back();
-      const rt4_region reg{0, 0, cw[q], ch[q], 0, 0};
-      if (light_gpus > 0) {
-        // the accumulator of the section from light_gpus devices; resolve and everything after it run here, on the root's
-        // accumulator, as in a one-GPU run
-        const char* fail_env = std::getenv("RT4_RENDER_FAIL_RANK");  // the test hooks of --gpus
-        const char* stage_env = std::getenv("RT4_RENDER_FAIL_STAGE");
-        const std::vector<unsigned char> acc =
-            render_light_shards(light_gpus, light_split == "bands", band, scene, lus, cw[q], ch[q], rehearse,
-                                fail_env ? std::atoi(fail_env) : -1, stage_env && std::strcmp(stage_env, "gather") == 0,
-                                &shards_count, &shards_ms);
-        HIP_CHECK(hipSetDevice(device));  // the rank threads chose their own
-        HIP_CHECK(hipMemcpy(d_light[q], acc.data(), acc.size(), hipMemcpyHostToDevice));
-      } else if (adaptive) {
-        // The loop of DESIGN.md §4.39 (Tracer.render_light_adaptive is the same loop): warm-up whole frames, then passes
-        // of the selected tiles, every ad_full_every-th pass and a pass with an empty selection a whole frame; frame g is
-        // rt4_progressive_uniforms(the section's uniforms with --seed, g), g running on across the passes.
-        rt4_uniforms ub;
-        cam.frame_number = frame_number;
-        RT4_CHECK(rt4_camera_frame_uniforms(&cam, &base[q], sections[q], static_cast<int32_t>(seed), &ub));
-        cam.frame_number = frame_number + static_cast<uint32_t>(frames);  // as the uniform frames above left it
-        const long long tiles = static_cast<long long>((cw[q] + 7) / 8) * ((ch[q] + 7) / 8);
-        const long long budget = static_cast<long long>(frames) * tiles;
-        uint32_t *d_tiles = nullptr, *d_n = nullptr;
-        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_tiles), static_cast<size_t>(tiles) * sizeof(uint32_t)));
-        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_n), sizeof(uint32_t)));
-        rt4_tile_select_params sel = ad_select;
-        sel.threshold = noise_threshold;
-        long long spent = 0;
-        uint32_t g = 0;
-        std::vector<rt4_uniforms> pus;
-        auto pass_uniforms = [&](int n) {
-          pus.resize(static_cast<size_t>(n));
-          for (int f = 0; f < n; f++) rt4_progressive_uniforms(&ub, ++g, &pus[static_cast<size_t>(f)]);
-        };
-        const int warm = std::min(ad_warmup, frames);
-        sel.min_frames = warm;
-        if (warm > 0) {
-          pass_uniforms(warm);
-          RT4_CHECK(rt4_render_light_device(ctx, pus.data(), warm, &reg, d_light[q], cw[q], d_count, nullptr, err, sizeof err));
-          spent += warm * tiles;
-          std::printf("adaptive %s: warmup tiles %lld frames %d\n", names[q], tiles, warm);
-        }
-        for (int n_pass = 1;; n_pass++) {
-          const char* kind = "full";
-          long long listed = tiles;
-          if (!(ad_full_every > 0 && n_pass % ad_full_every == 0)) {
-            RT4_CHECK(rt4_light_select_tiles_device(ctx, d_light[q], cw[q], cw[q], ch[q], ub.light_to_color_conversion_coefficient,
-                                                    &sel, d_tiles, d_n, nullptr, nullptr, err, sizeof err));
-            uint32_t n_sel = 0;  // the one 4-byte read of the pass (synchronises)
-            HIP_CHECK(hipMemcpy(&n_sel, d_n, sizeof n_sel, hipMemcpyDeviceToHost));
-            kind = n_sel == 0 ? "empty" : "tiles";
-            if (n_sel != 0) listed = n_sel;
-          }
-          const int n = static_cast<int>(std::min<long long>(ad_pass, (budget - spent) / listed));
-          if (n <= 0) break;
-          pass_uniforms(n);
-          if (listed == tiles && kind[0] != 't')
-            RT4_CHECK(rt4_render_light_device(ctx, pus.data(), n, &reg, d_light[q], cw[q], d_count, nullptr, err, sizeof err));
-          else
-            RT4_CHECK(rt4_render_light_tiles_device(ctx, pus.data(), n, &reg, d_tiles, static_cast<int32_t>(listed), d_light[q],
-                                                    cw[q], d_count, nullptr, err, sizeof err));
-          spent += n * listed;
-          std::printf("adaptive %s: %s tiles %lld frames %d\n", names[q], kind, listed, n);
-        }
-        light_issued = g;  // the loop's last frame number, whatever share of the image each frame covered
-        HIP_CHECK(hipDeviceSynchronize());
-        (void)hipFree(d_tiles);
-        (void)hipFree(d_n);
-      } else {
-        RT4_CHECK(rt4_render_light_device(ctx, lus.data(), frames, &reg, d_light[q], cw[q], d_count, nullptr, err, sizeof err));
-      }
-      RT4_CHECK(rt4_light_resolve_device(ctx, d_light[q], cw[q], base[q].light_to_color_conversion_coefficient, d_frame[q],
-                                         format, cw[q], cw[q], ch[q], nullptr, err, sizeof err));
-    }
-  }
-  if (pipelined) {
-    const rt4_region reg{0, 0, cw[0], ch[0], 0, 0};
-    RT4_CHECK(rt4_render_frames_device(ctx, us.data(), frames, &reg, d_frame[0], format, cw[0], d_count, nullptr, err,
-                                       sizeof err));
-  }
-  for (int n = 1; n <= frames && !pipelined && !light; n++) {
-    const int32_t s_n = static_cast<int32_t>(seed ^ (static_cast<uint32_t>(frames_done + n) * 0x9E3779B9u));
-    rt4_section_job jobs[3];
-    const uint32_t frame_number = cam.frame_number;
-    for (int q = 0; q < n_img; q++) {
-      cam.frame_number = frame_number;  // one frame: every section gets the same part
-      RT4_CHECK(rt4_camera_frame_uniforms(&cam, &base[q], sections[q], s_n, &jobs[q].u));
-      jobs[q].region = rt4_region{0, 0, cw[q], ch[q], 0, 0};
-      jobs[q].d_frame = d_frame[q];
-      jobs[q].row_stride_px = cw[q];
-      last_u[q] = jobs[q].u;
-      if (reproject) RT4_CHECK(rt4_temporal_frame_device(temporal[q], &jobs[q].u, nullptr, d_count, nullptr, err, sizeof err));
-    }
-    if (!reproject) RT4_CHECK(rt4_render_sections_device(ctx, jobs, n_img, format, d_count, nullptr, err, sizeof err));
-    if (keys && move_seconds > 0.0f) rt4_camera_move(&cam, keys, move_seconds);  // move(seconds), main.cpp:95-96
-  }
-  for (int q = 0; q < n_img && reproject; q++)  // the images written are the temporal images
-    HIP_CHECK(hipMemcpyAsync(d_frame[q], rt4_temporal_image(temporal[q]), static_cast<size_t>(cw[q]) * ch[q] * px,
-                             hipMemcpyDeviceToDevice, nullptr));
-  HIP_CHECK(hipEventRecord(e1, nullptr));
-  HIP_CHECK(hipEventSynchronize(e1));
-  float ms = 0.0f;
-  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  unsigned long long count = 0;
-  HIP_CHECK(hipMemcpy(&count, d_count, sizeof count, hipMemcpyDeviceToHost));
-  if (shards_ms >= 0.0) {  // --light-gpus: the ranks counted and timed the frames
-    ms = static_cast<float>(shards_ms);
-    count += shards_count;
-  }
+// --resume: the accumulator the run continues, refused rather than mixed with another run's frames
+void load_resumed(const Options& o, Run& r) {
+  const Section& s = r.sections[0];
+  uint32_t ck_seed = 0, ck_key = 0;
+  r.resumed.resize(s.frame_bytes(o.px()));
+  RT4_CHECK(rt4_accum_load(o.resume_path.c_str(), r.resumed.data(), o.format, s.w, s.h, s.w, &r.frames_done, &ck_seed, err,
+                           sizeof err));
+  if (ck_seed != o.seed) die("--resume", "the checkpoint was made with another --seed");
+  // the checkpoint's run key (scene, samples, bounces, resolution, camera ...): a checkpoint of
+  // another run would be blended in silently
+  RT4_CHECK(rt4_accum_key_of(o.resume_path.c_str(), &ck_key, err, sizeof err));
+  if (ck_key != 0u && ck_key != r.run_key) die("--resume", "the checkpoint was made with another scene, properties or camera");
+  r.cam.frame_number = static_cast<uint32_t>(r.frames_done + 1);
+}
 
-  for (int q = 0; q < n_img; q++) {
-    std::vector<unsigned char> host(static_cast<size_t>(cw[q]) * ch[q] * px);
-    HIP_CHECK(hipMemcpy(host.data(), d_frame[q], host.size(), hipMemcpyDeviceToHost));
-    const std::string path = out + "_" + names[q] + (png ? ".png" : ".ppm");
-    RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(path.c_str(), host.data(), format, cw[q], ch[q], cw[q], err, sizeof err));
-    if (raw) write_raw(out + "_" + names[q] + ".raw", host);
-    std::printf("wrote %s (%d x %d)\n", path.c_str(), cw[q], ch[q]);
-    rt4_gbuffer_px* d_gbuf = nullptr;  // --denoise: the G-buffer of the last pose and the filtered frame
-    void* d_dn = nullptr;
-    if (denoise_levels > 0 && frames >= 1) {
-      // the picture to look at: the final frame filtered along the primary hits of its camera pose (one G-buffer
-      // per pose and section); d_frame stays the accumulator
-      const size_t npx = static_cast<size_t>(cw[q]) * ch[q];
-      HIP_CHECK(hipMalloc(&d_gbuf, npx * sizeof(rt4_gbuffer_px)));
-      HIP_CHECK(hipMalloc(&d_dn, npx * px));
-      const rt4_region reg{0, 0, cw[q], ch[q], 0, 0};
-      rt4_denoise_params dp;
-      rt4_denoise_params_default(&dp);
-      dp.levels = denoise_levels;
-      // --reproject: the temporal object already holds the G-buffer of the last pose
-      if (!reproject) RT4_CHECK(rt4_render_gbuffer_device(ctx, &last_u[q], &reg, d_gbuf, cw[q], nullptr, err, sizeof err));
-      RT4_CHECK(rt4_denoise_device(ctx, d_frame[q], cw[q], d_dn, cw[q], format, cw[q], ch[q],
-                                   reproject ? rt4_temporal_gbuffer(temporal[q]) : d_gbuf, cw[q], &dp, nullptr, err, sizeof err));
-      HIP_CHECK(hipDeviceSynchronize());
-      std::vector<unsigned char> dn(host.size());
-      HIP_CHECK(hipMemcpy(dn.data(), d_dn, dn.size(), hipMemcpyDeviceToHost));
-      const std::string dn_path = out + "_" + names[q] + "_dn" + (png ? ".png" : ".ppm");
-      RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(dn_path.c_str(), dn.data(), format, cw[q], ch[q], cw[q], err, sizeof err));
-      if (raw) write_raw(out + "_" + names[q] + "_dn.raw", dn);
-      std::printf("wrote %s (%d x %d, %d filter levels)\n", dn_path.c_str(), cw[q], ch[q], denoise_levels);
+// --light-resume: the light accumulator the run continues (frames frames_done + 1 ...)
+void load_light_resumed(const Options& o, Run& r) {
+  const Section& s = r.sections[0];
+  const char* path = o.light_resume_path.c_str();
+  uint32_t ck_seed = 0, ck_key = 0, ck_flags = 0;
+  int32_t ck_w = 0, ck_h = 0;
+  RT4_CHECK(rt4_light_info(path, &ck_w, &ck_h, nullptr, &ck_seed, &ck_key, &ck_flags, err, sizeof err));
+  if (ck_flags & RT4_LIGHT_POOLED) die("--light-resume", "the checkpoint pools runs of several seeds: it cannot be resumed");
+  if (ck_w != s.w || ck_h != s.h)
+    die("--light-resume", ("the checkpoint holds a " + std::to_string(ck_w) + "x" + std::to_string(ck_h) + " accumulator, not " +
+                           std::to_string(s.w) + "x" + std::to_string(s.h)).c_str());
+  if (ck_seed != o.seed) die("--light-resume", "the checkpoint was made with another --seed");
+  if (ck_key != 0u && ck_key != r.run_key)
+    die("--light-resume", "the checkpoint was made with another scene, properties or camera");
+  r.light_start.resize(s.pixels());
+  RT4_CHECK(rt4_light_load(path, r.light_start.data(), s.w, s.h, s.w, &r.frames_done, nullptr, nullptr, nullptr, err,
+                           sizeof err));
+  if (r.frames_done + o.frames > 0xFFFFFFFFll) die("--light-resume", "frame numbers beyond 2^32 - 1");
+  r.cam.frame_number = static_cast<uint32_t>(r.frames_done + 1);
+}
+
+// --light-pool: the accumulators of independent runs, merged once there is a context. The main section takes its size
+// from the first file, while its uniforms (the tone curve's coefficient is what the outputs use) stay the properties'.
+void load_pool(const Options& o, Run& r) {
+  Section& s = r.sections[0];
+  std::vector<uint32_t> seeds;
+  for (size_t f = 0; f < o.light_pool.size(); f++) {
+    const char* path = o.light_pool[f].c_str();
+    int32_t fw = 0, fh = 0;
+    int64_t issued = 0;
+    uint32_t ck_seed = 0, ck_key = 0;
+    RT4_CHECK(rt4_light_info(path, &fw, &fh, &issued, &ck_seed, &ck_key, nullptr, err, sizeof err));
+    if (f == 0) {
+      s.w = fw, s.h = fh, r.pool_seed = ck_seed, r.pool_key = ck_key, r.pool_issued = issued;
+      r.light_start.resize(o.light_pool.size() * s.pixels());
     }
-    if (light_denoise_levels >= 0 && frames >= 1) {
-      // --light-denoise: the section's light accumulator filtered along the primary hits of its pose, with each
-      // pixel's own standard error as the luminance tolerance, and tone-mapped once; the accumulator is only read
-      const size_t npx = static_cast<size_t>(cw[q]) * ch[q];
-      HIP_CHECK(hipMalloc(&d_gbuf, npx * sizeof(rt4_gbuffer_px)));
-      HIP_CHECK(hipMalloc(&d_dn, npx * px));
-      const rt4_region reg{0, 0, cw[q], ch[q], 0, 0};
-      rt4_light_denoise_params lp;
-      rt4_light_denoise_params_default(&lp);
-      lp.levels = light_denoise_levels;
-      RT4_CHECK(rt4_render_gbuffer_device(ctx, &last_u[q], &reg, d_gbuf, cw[q], nullptr, err, sizeof err));
-      RT4_CHECK(rt4_light_denoise_device(ctx, d_light[q], cw[q], d_gbuf, cw[q], base[q].light_to_color_conversion_coefficient,
-                                         &lp, d_dn, format, cw[q], nullptr, 0, cw[q], ch[q], nullptr, err, sizeof err));
-      HIP_CHECK(hipDeviceSynchronize());
-      std::vector<unsigned char> dn(host.size());
-      HIP_CHECK(hipMemcpy(dn.data(), d_dn, dn.size(), hipMemcpyDeviceToHost));
-      const std::string dn_path = out + "_" + names[q] + "_ldn" + (png ? ".png" : ".ppm");
-      RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(dn_path.c_str(), dn.data(), format, cw[q], ch[q], cw[q], err, sizeof err));
-      if (raw) write_raw(out + "_" + names[q] + "_ldn.raw", dn);
-      std::printf("wrote %s (%d x %d, %d light filter levels)\n", dn_path.c_str(), cw[q], ch[q], light_denoise_levels);
-    }
-    if (window_scale != 0 && frames >= 1) {
-      // what the reference's window shows: the cell image (filtered, if it was) stretched over cells * scale pixels,
-      // interpolated along the window pixels' own primary hits unless --window-nearest
-      const int32_t sc = win_scale[q], ww = cw[q] * sc, wh = ch[q] * sc;
-      rt4_window* win = nullptr;
-      RT4_CHECK(rt4_window_create(ctx, cw[q], ch[q], sc, format, &win, err, sizeof err));
-      rt4_upscale_params up;
-      rt4_upscale_params_default(&up);
-      if (window_nearest) up.mode = RT4_UPSCALE_NEAREST;
-      // a cell G-buffer of the last pose that already exists is passed on; otherwise the window renders its own
-      const rt4_gbuffer_px* d_gcells = reproject ? rt4_temporal_gbuffer(temporal[q]) : d_dn ? d_gbuf : nullptr;
-      RT4_CHECK(rt4_window_present_device(win, &last_u[q], d_dn ? d_dn : d_frame[q], cw[q], d_gcells, cw[q], &up, nullptr, err,
-                                          sizeof err));
-      std::vector<unsigned char> wimg(static_cast<size_t>(ww) * wh * px);
-      RT4_CHECK(rt4_window_read_host(win, wimg.data(), nullptr, err, sizeof err));
-      const std::string win_path = out + "_" + names[q] + "_win" + (png ? ".png" : ".ppm");
-      RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(win_path.c_str(), wimg.data(), format, ww, wh, ww, err, sizeof err));
-      if (raw) write_raw(out + "_" + names[q] + "_win.raw", wimg);
-      std::printf("wrote %s (%d x %d, scale %d, %s)\n", win_path.c_str(), ww, wh, sc, window_nearest ? "nearest" : "guided");
-      rt4_window_destroy(win);
-    }
-    if (d_gbuf) (void)hipFree(d_gbuf);
-    if (d_dn) (void)hipFree(d_dn);
-    if (light) {
-      // the error estimate of the section: its statistics and, with --noise-map, the display error q as grey
-      const size_t npx = static_cast<size_t>(cw[q]) * ch[q];
-      if (raw || (q == 0 && !light_checkpoint_path.empty())) {
-        // --raw: the accumulator's bytes too; --light-checkpoint: the accumulator with what a resume or a pool must know
-        std::vector<unsigned char> acc(npx * sizeof(rt4_light_px));
-        HIP_CHECK(hipMemcpy(acc.data(), d_light[q], acc.size(), hipMemcpyDeviceToHost));
-        if (raw) write_raw(out + "_" + names[q] + "_light.raw", acc);
-        if (q == 0 && !light_checkpoint_path.empty()) {
-          RT4_CHECK(rt4_light_save(light_checkpoint_path.c_str(), reinterpret_cast<const rt4_light_px*>(acc.data()), cw[0], ch[0],
-                                   cw[0], light_issued, pool ? pool_seed : seed, pool ? pool_key : run_key,
-                                   pool ? RT4_LIGHT_POOLED : 0u, err, sizeof err));
-          std::printf("light checkpoint %s (frames issued %lld%s)\n", light_checkpoint_path.c_str(),
-                      static_cast<long long>(light_issued), pool ? ", pooled" : "");
-        }
-      }
-      float* d_q = nullptr;
-      rt4_noise_stats* d_stats = nullptr;
-      if (noise_map) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_q), npx * sizeof(float)));
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_stats), sizeof(rt4_noise_stats)));
-      RT4_CHECK(rt4_light_noise_device(ctx, d_light[q], cw[q], cw[q], ch[q], base[q].light_to_color_conversion_coefficient,
-                                       noise_threshold, nullptr, d_q, cw[q], nullptr, d_stats, nullptr, err, sizeof err));
-      HIP_CHECK(hipDeviceSynchronize());
-      rt4_noise_stats ns;
-      HIP_CHECK(hipMemcpy(&ns, d_stats, sizeof ns, hipMemcpyDeviceToHost));
-      if (noise_map) {
-        std::vector<float> qv(npx), grey(npx * 4);
-        HIP_CHECK(hipMemcpy(qv.data(), d_q, npx * sizeof(float), hipMemcpyDeviceToHost));
-        for (size_t p = 0; p < npx; p++) {  // the writers clamp to [0, 1]: an unmeasured pixel (+inf) is white; NaN black
-          const float v = std::isnan(qv[p]) ? 0.0f : qv[p];
-          grey[4 * p] = grey[4 * p + 1] = grey[4 * p + 2] = v;
-          grey[4 * p + 3] = 1.0f;
-        }
-        const std::string q_path = out + "_" + names[q] + "_q" + (png ? ".png" : ".ppm");
-        RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(q_path.c_str(), grey.data(), RT4_FRAME_RGBA32F, cw[q], ch[q], cw[q], err,
-                                                        sizeof err));
-        std::printf("wrote %s (%d x %d, display error q)\n", q_path.c_str(), cw[q], ch[q]);
-        (void)hipFree(d_q);
-      }
-      (void)hipFree(d_stats);
-      std::printf("noise %s: pixels %llu, measured %llu, above %llu (threshold %.6g), max_q %.6g, max_se %.6g\n", names[q],
-                  static_cast<unsigned long long>(ns.pixels), static_cast<unsigned long long>(ns.measured),
-                  static_cast<unsigned long long>(ns.above), static_cast<double>(noise_threshold),
-                  static_cast<double>(ns.max_q), static_cast<double>(ns.max_se));
-      if (adaptive) {
-        // where the frames went: min / median / max of n, and n over the largest n as grey
-        std::vector<rt4_light_px> acc(npx);
-        HIP_CHECK(hipMemcpy(acc.data(), d_light[q], npx * sizeof(rt4_light_px), hipMemcpyDeviceToHost));
-        std::vector<int32_t> nv(npx);
-        for (size_t p = 0; p < npx; p++) nv[p] = acc[p].n;
-        std::vector<int32_t> sorted = nv;
-        std::sort(sorted.begin(), sorted.end());
-        const int32_t n_max = sorted.back();
-        std::vector<float> grey(npx * 4);
-        for (size_t p = 0; p < npx; p++) {
-          grey[4 * p] = grey[4 * p + 1] = grey[4 * p + 2] = n_max > 0 ? static_cast<float>(nv[p]) / static_cast<float>(n_max) : 0.0f;
-          grey[4 * p + 3] = 1.0f;
-        }
-        const std::string n_path = out + "_" + names[q] + "_n" + (png ? ".png" : ".ppm");
-        RT4_CHECK((png ? rt4_write_png : rt4_write_ppm)(n_path.c_str(), grey.data(), RT4_FRAME_RGBA32F, cw[q], ch[q], cw[q], err,
-                                                        sizeof err));
-        std::printf("wrote %s (%d x %d, frames per pixel)\n", n_path.c_str(), cw[q], ch[q]);
-        std::printf("adaptive %s: n min %d, median %d, max %d\n", names[q], sorted.front(), sorted[npx / 2], n_max);
-      }
-    }
-    if (q == 0 && !checkpoint_path.empty()) {
-      // frames_done counts camera-resting frames only: a moving camera restarts the blend (frame_number 1)
-      RT4_CHECK(rt4_accum_save_key(checkpoint_path.c_str(), host.data(), format, cw[0], ch[0], cw[0],
-                                   static_cast<int64_t>(cam.frame_number) - 1, seed, run_key, err, sizeof err));
-      std::printf("checkpoint %s (%lld frames)\n", checkpoint_path.c_str(), static_cast<long long>(cam.frame_number) - 1);
-    }
+    if (fw != s.w || fh != s.h) die("--light-pool: another image size than the first file's", path);
+    if (ck_key != r.pool_key) die("--light-pool: another scene, properties or camera than the first file's", path);
+    if (std::find(seeds.begin(), seeds.end(), ck_seed) != seeds.end())
+      die("--light-pool: the same --seed as an earlier file, the same frames would count twice", path);
+    seeds.push_back(ck_seed);
+    RT4_CHECK(rt4_light_load(path, r.light_start.data() + f * s.pixels(), fw, fh, fw, nullptr, nullptr, nullptr, nullptr, err,
+                             sizeof err));
   }
-  if (pool)
-    std::printf("pooled %zu light checkpoints, images 1\n", light_pool.size());
-  else if (light_gpus > 0)
-    std::printf("light gpus %d (%s), frames %d, images 1, intersections %llu, %.3f ms/frame, %.3e intersections/s\n", light_gpus,
-                light_split.c_str(), frames, count, ms / frames, static_cast<double>(count) / (ms * 1e-3));
+}
+
+// Step 1: properties, scene, sections, camera, the run's key, and the checkpoints of --resume, --light-resume, --light-pool.
+Run load_inputs(const Options& o) {
+  Run r;
+  RT4_CHECK(rt4_properties_load(o.props_path.c_str(), &r.props, err, sizeof err));
+  // scene: -s builtin name or .frag path; else the properties' shader_filename (main.cpp:26)
+  r.scene = static_cast<rt4_scene_desc*>(std::calloc(1, sizeof(rt4_scene_desc)));
+  std::string scene_arg = o.scene_arg;
+  if (scene_arg.empty()) {
+    char buf[4096];
+    size_t need = 0;
+    RT4_CHECK(rt4_properties_get_string(r.props, "shader_filename", buf, sizeof buf, &need, err, sizeof err));
+    scene_arg = buf;
+  }
+  if (scene_arg.size() > 5 && scene_arg.compare(scene_arg.size() - 5, 5, ".frag") == 0)
+    RT4_CHECK(rt4_scene_load_frag(scene_arg.c_str(), r.scene, err, sizeof err));
   else
-    std::printf("frames %d, images %d, intersections %llu, %.3f ms/frame, %.3e intersections/s\n", frames, n_img,
-                count, ms / frames, static_cast<double>(count) / (ms * 1e-3));
+    RT4_CHECK(rt4_scene_builtin(scene_arg.c_str(), r.scene, err, sizeof err));
 
-  for (int q = 0; q < n_img; q++) rt4_temporal_destroy(temporal[q]);
-  for (int q = 0; q < n_img; q++)
-    if (d_light[q]) (void)hipFree(d_light[q]);
-  for (int q = 0; q < n_img; q++) (void)hipFree(d_frame[q]);
-  (void)hipFree(d_count);
-  rt4_context_destroy(ctx);
-  rt4_properties_free(props);
-  std::free(scene);
+  static const Section kinds[3] = {{RT4_SECTION_YXZ, "yxz", "main"}, {RT4_SECTION_YWZ, "ywz", "additional"},
+                                   {RT4_SECTION_YXW, "yxw", "additional"}};
+  r.sections.assign(kinds, kinds + (o.three ? 3 : 1));
+  Section& yxz = r.sections[0];
+  const bool sized = o.width > 0 && o.height > 0;  // -W -H: the main section's cells, in place of the properties'
+  for (Section& s : r.sections)
+    if (!(sized && &s == &yxz)) RT4_CHECK(rt4_window_cells(r.props, s.window, &s.w, &s.h, err, sizeof err));
+  if (sized) yxz.w = o.width, yxz.h = o.height;
+  for (Section& s : r.sections)
+    RT4_CHECK(rt4_uniforms_from_properties(r.props, s.w, s.h, s.id, &s.base, nullptr, err, sizeof err));
+  RT4_CHECK(rt4_camera_init(r.props, &r.cam, err, sizeof err));
+  rt4_camera c0 = r.cam;
+  rt4_uniforms u0;
+  RT4_CHECK(rt4_camera_frame_uniforms(&c0, &yxz.base, yxz.id, 0, &u0));
+  r.run_key = rt4_accum_key(r.scene, &u0);
+
+  if (!o.resume_path.empty()) load_resumed(o, r);
+  if (!o.light_resume_path.empty()) load_light_resumed(o, r);
+  if (o.pool()) load_pool(o, r);
+  return r;
+}
+
+// --window: every section's scale, the flag's or the cell_size of the section's window in the properties
+void window_scales(const Options& o, Run& r) {
+  for (Section& s : r.sections) {
+    s.win_scale = o.window_scale;
+    const std::string key = std::string("window.") + s.window + ".cell_size";
+    if (o.window_scale < 0) RT4_CHECK(rt4_properties_get_int(r.props, key.c_str(), &s.win_scale, err, sizeof err));
+  }
+}
+
+// The seed of progressive frame n, counted from the run's first frame (a resumed run passes frames_done + n):
+// main.cpp's seed ^= generateSeed(timer), deterministic.
+int32_t frame_seed(uint32_t seed, int64_t n) { return static_cast<int32_t>(seed ^ (static_cast<uint32_t>(n) * 0x9E3779B9u)); }
+
+// The uniforms of the run's -n frames of a section with a resting camera; the camera's frame number moves on by -n.
+std::vector<rt4_uniforms> resting_frames(const Options& o, Run& r, const Section& s) {
+  std::vector<rt4_uniforms> us(static_cast<size_t>(std::max(o.frames, 0)));
+  for (int64_t n = 1; n <= o.frames; n++)
+    RT4_CHECK(rt4_camera_frame_uniforms(&r.cam, &s.base, s.id, frame_seed(o.seed, r.frames_done + n), &us[n - 1]));
+  return us;
+}
+
+void write_raw(const std::string& path, const void* data, size_t bytes) {  // --raw
+  std::FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) die("--raw", path.c_str());
+  const bool ok = std::fwrite(data, 1, bytes, f) == bytes;
+  if (std::fclose(f) != 0 || !ok) die("--raw: write failed", path.c_str());
+}
+
+// One image of a section, <prefix>_<section><suffix>.png or .ppm: w x h pixels of `format` in `bytes` bytes at data.
+// raw_twin: with --raw also the bytes themselves, <prefix>_<section><suffix>.raw. Then the line "wrote <path>
+// (<w> x <h><note>)"; a note starts with ", ".
+void write_image(const Options& o, const char* section, const char* suffix, const void* data, size_t bytes, int32_t format,
+                 int32_t w, int32_t h, bool raw_twin, const std::string& note) {
+  const std::string stem = o.out + "_" + section + suffix, path = stem + (o.png ? ".png" : ".ppm");
+  RT4_CHECK((o.png ? rt4_write_png : rt4_write_ppm)(path.c_str(), data, format, w, h, w, err, sizeof err));
+  if (raw_twin && o.raw) write_raw(stem + ".raw", data, bytes);
+  std::printf("wrote %s (%d x %d%s)\n", path.c_str(), w, h, note.c_str());
+}
+
+// One value per pixel as an opaque grey fp32 frame (the _q and _n maps; the writers clamp to [0, 1]).
+std::vector<float> grey_image(const std::vector<float>& values) {
+  std::vector<float> grey(values.size() * 4, 1.0f);
+  for (size_t p = 0; p < values.size(); p++) grey[4 * p] = grey[4 * p + 1] = grey[4 * p + 2] = values[p];
+  return grey;
+}
+
+template <class T> T* device_alloc(size_t n, bool zeroed = false) {
+  void* p = nullptr;
+  HIP_CHECK(hipMalloc(&p, n * sizeof(T)));
+  if (zeroed) HIP_CHECK(hipMemset(p, 0, n * sizeof(T)));
+  return static_cast<T*>(p);
+}
+
+template <class T> std::vector<T> device_read(const void* d, size_t n) {
+  std::vector<T> host(n);
+  HIP_CHECK(hipMemcpy(host.data(), d, n * sizeof(T), hipMemcpyDeviceToHost));
+  return host;
+}
+
+// The run in one line; gpus: what a multi-GPU run puts in front ("gpus 3, ").
+void print_summary(const std::string& gpus, int frames, size_t images, unsigned long long count, double ms_per_frame, double ms) {
+  std::printf("%sframes %d, images %zu, intersections %llu, %.3f ms/frame, %.3e intersections/s\n", gpus.c_str(), frames, images,
+              count, ms_per_frame, static_cast<double>(count) / (ms * 1e-3));
+}
+
+// Step 2 with --gpus: the whole run. Pixel bands over GPUs 0..gpus-1, one RCCL gather, the image and the summary. The
+// ranks create their own contexts; none is created here.
+void run_bands(const Options& o, const ShardHooks& hooks, Run& r) {
+  const Section& s = r.sections[0];
+  const ShardResult res =
+      render_bands(o.gpus, o.band, r.scene, resting_frames(o, r, s), s.w, s.h, o.format, o.frame_by_frame, hooks);
+  write_image(o, s.name, "", res.image.data(), res.image.size(), o.format, s.w, s.h, true, "");
+  print_summary("gpus " + std::to_string(o.gpus) + ", ", o.frames, 1, res.count, res.ms / o.frames, res.ms);
+}
+
+// Step 2 on one GPU: the context, every section's cleared frame (the --resume frame in the main one), the counter, and
+// with --reproject one rt4_temporal per section.
+void open_render(const Options& o, Run& r) {
+  RT4_CHECK(rt4_context_create(o.device, RT4_FLAG_SAMPLER_LUT, &r.ctx, err, sizeof err));
+  RT4_CHECK(rt4_context_set_scene(r.ctx, r.scene, err, sizeof err));
+  for (Section& s : r.sections) s.d_frame = device_alloc<unsigned char>(s.frame_bytes(o.px()), true);  // cleared RenderTexture
+  if (!r.resumed.empty()) HIP_CHECK(hipMemcpy(r.sections[0].d_frame, r.resumed.data(), r.resumed.size(), hipMemcpyHostToDevice));
+  r.d_count = device_alloc<unsigned long long>(1, true);
+  HIP_CHECK(hipEventCreate(&r.e0));
+  HIP_CHECK(hipEventCreate(&r.e1));
+  for (Section& s : r.sections)
+    if (o.reproject) RT4_CHECK(rt4_temporal_create(r.ctx, s.w, s.h, o.format, &s.temporal, err, sizeof err));
+}
+
+// The pipelined run's frames, and the frame-colour scratch only when frames are actually pipelined (>= 2 frames, a
+// scene that does not run frame by frame), and only for the frames of one chunk.
+void pipelined_frames(const Options& o, Run& r) {
+  Section& s = r.sections[0];
+  if (o.frames >= 2 && rt4_context_frames_per_launch(r.ctx, s.w, s.h) > 1)
+    RT4_CHECK(rt4_context_reserve_frames(r.ctx, s.w, s.h, err, sizeof err));
+  r.us = resting_frames(o, r, s);
+  if (!r.us.empty()) s.last_u = r.us.back();
+}
+
+// --light: one empty accumulator per section; the main one continues --light-resume's, or is --light-pool's files
+// merged in order, RT4_LIGHT_MERGE_MAX of them per call, and resolved into the section's frame.
+void open_light(const Options& o, Run& r) {
+  for (Section& s : r.sections) s.d_light = device_alloc<rt4_light_px>(s.pixels(), true);
+  Section& s = r.sections[0];
+  const size_t bytes = s.pixels() * sizeof(rt4_light_px);
+  r.light_issued = o.pool() ? r.pool_issued : r.frames_done + o.frames;
+  if (!o.light_resume_path.empty()) HIP_CHECK(hipMemcpy(s.d_light, r.light_start.data(), bytes, hipMemcpyHostToDevice));
+  if (!o.pool()) return;
+  std::vector<rt4_light_px> merged(s.pixels());  // empty: value-initialised
+  const int64_t plane = static_cast<int64_t>(s.pixels());
+  for (size_t f0 = 0; f0 < o.light_pool.size(); f0 += RT4_LIGHT_MERGE_MAX)
+    RT4_CHECK(rt4_light_merge_host(r.ctx, merged.data(), s.w, r.light_start.data() + f0 * s.pixels(), s.w, plane,
+                                   static_cast<int32_t>(std::min<size_t>(RT4_LIGHT_MERGE_MAX, o.light_pool.size() - f0)), s.w,
+                                   s.h, err, sizeof err));
+  HIP_CHECK(hipMemcpy(s.d_light, merged.data(), bytes, hipMemcpyHostToDevice));
+  RT4_CHECK(rt4_light_resolve_device(r.ctx, s.d_light, s.w, s.tone(), s.d_frame, o.format, s.w, s.w, s.h, nullptr, err,
+                                     sizeof err));
+}
+
+// --adaptive, one section: the loop of DESIGN.md §4.39 (Tracer.render_light_adaptive is the same loop): warm-up whole
+// frames, then passes of the selected tiles, every ad_full_every-th pass and a pass with an empty selection a whole
+// frame; frame g is rt4_progressive_uniforms(ub: the section's uniforms with --seed, g), g running on across the
+// passes. Returns the loop's last frame number, whatever share of the image each frame covered.
+uint32_t adaptive_passes(const Options& o, Run& r, const Section& s, const rt4_uniforms& ub) {
+  const rt4_region reg = s.region();
+  const long long tiles = static_cast<long long>((s.w + 7) / 8) * ((s.h + 7) / 8);
+  const long long budget = static_cast<long long>(o.frames) * tiles;
+  uint32_t* d_tiles = device_alloc<uint32_t>(static_cast<size_t>(tiles));
+  uint32_t* d_n = device_alloc<uint32_t>(1);
+  rt4_tile_select_params sel = o.ad_select;
+  sel.threshold = o.noise_threshold;
+  long long spent = 0;
+  uint32_t g = 0;
+  std::vector<rt4_uniforms> pus;
+  auto pass_uniforms = [&](int n) {
+    pus.resize(static_cast<size_t>(n));
+    for (int f = 0; f < n; f++) rt4_progressive_uniforms(&ub, ++g, &pus[static_cast<size_t>(f)]);
+  };
+  const int warm = std::min(o.ad_warmup, o.frames);
+  sel.min_frames = warm;
+  if (warm > 0) {
+    pass_uniforms(warm);
+    RT4_CHECK(rt4_render_light_device(r.ctx, pus.data(), warm, &reg, s.d_light, s.w, r.d_count, nullptr, err, sizeof err));
+    spent += warm * tiles;
+    std::printf("adaptive %s: warmup tiles %lld frames %d\n", s.name, tiles, warm);
+  }
+  for (int n_pass = 1;; n_pass++) {
+    const char* kind = "full";
+    long long listed = tiles;
+    if (!(o.ad_full_every > 0 && n_pass % o.ad_full_every == 0)) {
+      RT4_CHECK(rt4_light_select_tiles_device(r.ctx, s.d_light, s.w, s.w, s.h, ub.light_to_color_conversion_coefficient, &sel,
+                                              d_tiles, d_n, nullptr, nullptr, err, sizeof err));
+      uint32_t n_sel = 0;  // the one 4-byte read of the pass (synchronises)
+      HIP_CHECK(hipMemcpy(&n_sel, d_n, sizeof n_sel, hipMemcpyDeviceToHost));
+      kind = n_sel == 0 ? "empty" : "tiles";
+      if (n_sel != 0) listed = n_sel;
+    }
+    const int n = static_cast<int>(std::min<long long>(o.ad_pass, (budget - spent) / listed));
+    if (n <= 0) break;
+    pass_uniforms(n);
+    if (listed == tiles && kind[0] != 't')  // a selection that lists every tile still goes through the tile path
+      RT4_CHECK(rt4_render_light_device(r.ctx, pus.data(), n, &reg, s.d_light, s.w, r.d_count, nullptr, err, sizeof err));
+    else
+      RT4_CHECK(rt4_render_light_tiles_device(r.ctx, pus.data(), n, &reg, d_tiles, static_cast<int32_t>(listed), s.d_light, s.w,
+                                              r.d_count, nullptr, err, sizeof err));
+    spent += n * listed;
+    std::printf("adaptive %s: %s tiles %lld frames %d\n", s.name, kind, listed, n);
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+  (void)hipFree(d_tiles);
+  (void)hipFree(d_n);
+  return g;
+}
+
+// --light, one section: its frames into its accumulator (frame n of every section has the same seed, as in
+// render_colour_frames) in one of three ways, then the image: the accumulator resolved into the section's frame.
+// frame_number: the camera's before the first section, so that every section renders the same frames.
+void render_light_section(const Options& o, const ShardHooks& hooks, Run& r, Section& s, uint32_t frame_number) {
+  r.cam.frame_number = frame_number;
+  const std::vector<rt4_uniforms> lus = resting_frames(o, r, s);
+  s.last_u = lus.back();
+  const rt4_region reg = s.region();
+  if (o.light_gpus > 0) {
+    // the accumulator of the section from light_gpus devices; resolve and everything after it run here, on the root's
+    // accumulator, as in a one-GPU run
+    const ShardResult acc = render_light_shards(o.light_gpus, o.light_split == "bands", o.band, r.scene, lus, s.w, s.h, hooks);
+    r.shards_count = acc.count, r.shards_ms = acc.ms;
+    HIP_CHECK(hipSetDevice(o.device));  // the rank threads chose their own
+    HIP_CHECK(hipMemcpy(s.d_light, acc.image.data(), acc.image.size(), hipMemcpyHostToDevice));
+  } else if (o.adaptive) {
+    rt4_uniforms ub;
+    r.cam.frame_number = frame_number;
+    RT4_CHECK(rt4_camera_frame_uniforms(&r.cam, &s.base, s.id, static_cast<int32_t>(o.seed), &ub));
+    r.cam.frame_number = frame_number + static_cast<uint32_t>(o.frames);  // as the uniform frames above left it
+    r.light_issued = adaptive_passes(o, r, s, ub);
+  } else {
+    RT4_CHECK(rt4_render_light_device(r.ctx, lus.data(), o.frames, &reg, s.d_light, s.w, r.d_count, nullptr, err, sizeof err));
+  }
+  RT4_CHECK(rt4_light_resolve_device(r.ctx, s.d_light, s.w, s.tone(), s.d_frame, o.format, s.w, s.w, s.h, nullptr, err,
+                                     sizeof err));
+}
+
+// The colour frames: pipelined (us: pipelined_frames), or frame by frame: all sections of a frame in one launch, the
+// camera moved after it (--keys), or with --reproject every section's frame through its rt4_temporal, whose images
+// are then the images written.
+void render_colour_frames(const Options& o, Run& r) {
+  if (o.pipelined()) {
+    const Section& s = r.sections[0];
+    const rt4_region reg = s.region();
+    RT4_CHECK(rt4_render_frames_device(r.ctx, r.us.data(), o.frames, &reg, s.d_frame, o.format, s.w, r.d_count, nullptr, err,
+                                       sizeof err));
+    return;
+  }
+  const int n_img = static_cast<int>(r.sections.size());
+  for (int n = 1; n <= o.frames; n++) {
+    rt4_section_job jobs[3];
+    const uint32_t frame_number = r.cam.frame_number;
+    for (int q = 0; q < n_img; q++) {
+      Section& s = r.sections[static_cast<size_t>(q)];
+      r.cam.frame_number = frame_number;  // one frame: every section gets the same part
+      RT4_CHECK(rt4_camera_frame_uniforms(&r.cam, &s.base, s.id, frame_seed(o.seed, r.frames_done + n), &jobs[q].u));
+      jobs[q].region = s.region();
+      jobs[q].d_frame = s.d_frame;
+      jobs[q].row_stride_px = s.w;
+      s.last_u = jobs[q].u;
+      if (o.reproject) RT4_CHECK(rt4_temporal_frame_device(s.temporal, &jobs[q].u, nullptr, r.d_count, nullptr, err, sizeof err));
+    }
+    if (!o.reproject) RT4_CHECK(rt4_render_sections_device(r.ctx, jobs, n_img, o.format, r.d_count, nullptr, err, sizeof err));
+    if (o.moving()) rt4_camera_move(&r.cam, o.keys, o.move_seconds);  // move(seconds), main.cpp:95-96
+  }
+  if (!o.reproject) return;
+  for (Section& s : r.sections)  // the images written are the temporal images
+    HIP_CHECK(hipMemcpyAsync(s.d_frame, rt4_temporal_image(s.temporal), s.frame_bytes(o.px()), hipMemcpyDeviceToDevice, nullptr));
+}
+
+// Step 3: every frame of every section between two event records, and what they counted and took.
+void render_frames(const Options& o, const ShardHooks& hooks, Run& r) {
+  HIP_CHECK(hipEventRecord(r.e0, nullptr));
+  const uint32_t frame_number = r.cam.frame_number;
+  for (Section& s : r.sections)
+    if (o.light && o.frames >= 1) render_light_section(o, hooks, r, s, frame_number);
+  if (!o.light) render_colour_frames(o, r);
+  HIP_CHECK(hipEventRecord(r.e1, nullptr));
+  HIP_CHECK(hipEventSynchronize(r.e1));
+  HIP_CHECK(hipEventElapsedTime(&r.ms, r.e0, r.e1));
+  HIP_CHECK(hipMemcpy(&r.count, r.d_count, sizeof r.count, hipMemcpyDeviceToHost));
+  // --light-gpus: the ranks counted and timed the frames
+  if (r.shards_ms >= 0.0) r.ms = static_cast<float>(r.shards_ms), r.count += r.shards_count;
+}
+
+// --denoise / --light-denoise, one section: <name>_dn / <name>_ldn, the picture to look at. The final frame filtered
+// along the primary hits of its camera pose (one G-buffer per pose and section; --reproject: the temporal object
+// already holds it), or the light accumulator filtered along them with each pixel's own standard error as the
+// luminance tolerance and tone-mapped once. d_frame and d_light are only read. d_gbuf and d_dn stay for --window.
+void filtered_frame(const Options& o, Run& r, const Section& s, rt4_gbuffer_px*& d_gbuf, void*& d_dn) {
+  const int32_t format = o.format, px = o.px();
+  const bool of_light = o.light_denoise_levels >= 0;
+  d_gbuf = device_alloc<rt4_gbuffer_px>(s.pixels());
+  d_dn = device_alloc<unsigned char>(s.frame_bytes(px));
+  const rt4_region reg = s.region();
+  if (!o.reproject) RT4_CHECK(rt4_render_gbuffer_device(r.ctx, &s.last_u, &reg, d_gbuf, s.w, nullptr, err, sizeof err));
+  if (of_light) {
+    rt4_light_denoise_params lp = defaults(rt4_light_denoise_params_default);
+    lp.levels = o.light_denoise_levels;
+    RT4_CHECK(rt4_light_denoise_device(r.ctx, s.d_light, s.w, d_gbuf, s.w, s.tone(), &lp, d_dn, format, s.w, nullptr, 0, s.w, s.h,
+                                       nullptr, err, sizeof err));
+  } else {
+    rt4_denoise_params dp = defaults(rt4_denoise_params_default);
+    dp.levels = o.denoise_levels;
+    RT4_CHECK(rt4_denoise_device(r.ctx, s.d_frame, s.w, d_dn, s.w, format, s.w, s.h,
+                                 o.reproject ? rt4_temporal_gbuffer(s.temporal) : d_gbuf, s.w, &dp, nullptr, err, sizeof err));
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+  const std::vector<unsigned char> dn = device_read<unsigned char>(d_dn, s.frame_bytes(px));
+  const int levels = of_light ? o.light_denoise_levels : o.denoise_levels;
+  write_image(o, s.name, of_light ? "_ldn" : "_dn", dn.data(), dn.size(), format, s.w, s.h, true,
+              ", " + std::to_string(levels) + (of_light ? " light filter levels" : " filter levels"));
+}
+
+// --window, one section: <name>_win, what the reference's window shows: the cell image (d_dn, the filtered one, if
+// there is one) stretched over cells * scale pixels, interpolated along the window pixels' own primary hits unless
+// --window-nearest. A cell G-buffer of the last pose that already exists is passed on (the temporal one with
+// --reproject, else d_gbuf when a filter ran); otherwise the window renders its own.
+void window_image(const Options& o, Run& r, const Section& s, const rt4_gbuffer_px* d_gbuf, const void* d_dn) {
+  const int32_t sc = s.win_scale, ww = s.w * sc, wh = s.h * sc, format = o.format;
+  rt4_window* win = nullptr;
+  RT4_CHECK(rt4_window_create(r.ctx, s.w, s.h, sc, format, &win, err, sizeof err));
+  rt4_upscale_params up = defaults(rt4_upscale_params_default);
+  if (o.window_nearest) up.mode = RT4_UPSCALE_NEAREST;
+  const rt4_gbuffer_px* d_cells = o.reproject ? rt4_temporal_gbuffer(s.temporal) : d_dn ? d_gbuf : nullptr;
+  RT4_CHECK(rt4_window_present_device(win, &s.last_u, d_dn ? d_dn : s.d_frame, s.w, d_cells, s.w, &up, nullptr, err, sizeof err));
+  std::vector<unsigned char> wimg(static_cast<size_t>(ww) * wh * o.px());
+  RT4_CHECK(rt4_window_read_host(win, wimg.data(), nullptr, err, sizeof err));
+  write_image(o, s.name, "_win", wimg.data(), wimg.size(), format, ww, wh, true,
+              ", scale " + std::to_string(sc) + (o.window_nearest ? ", nearest" : ", guided"));
+  rt4_window_destroy(win);
+}
+
+// --light, one section: with --raw the accumulator's bytes, from the main section --light-checkpoint (the accumulator
+// with what a resume or a pool must know), the error estimate (the statistics and, with --noise-map, the display
+// error q as grey) and, with --adaptive, where the frames went: min / median / max of n, and n over the largest as grey.
+void light_outputs(const Options& o, Run& r, const Section& s) {
+  const size_t npx = s.pixels();
+  const bool checkpoint = s.id == RT4_SECTION_YXZ && !o.light_checkpoint_path.empty();
+  std::vector<rt4_light_px> acc;
+  if (o.raw || checkpoint || o.adaptive) acc = device_read<rt4_light_px>(s.d_light, npx);
+  if (o.raw) write_raw(o.out + "_" + s.name + "_light.raw", acc.data(), npx * sizeof(rt4_light_px));
+  if (checkpoint) {
+    RT4_CHECK(rt4_light_save(o.light_checkpoint_path.c_str(), acc.data(), s.w, s.h, s.w, r.light_issued,
+                             o.pool() ? r.pool_seed : o.seed, o.pool() ? r.pool_key : r.run_key, o.pool() ? RT4_LIGHT_POOLED : 0u,
+                             err, sizeof err));
+    std::printf("light checkpoint %s (frames issued %lld%s)\n", o.light_checkpoint_path.c_str(),
+                static_cast<long long>(r.light_issued), o.pool() ? ", pooled" : "");
+  }
+  float* d_q = o.noise_map ? device_alloc<float>(npx) : nullptr;
+  rt4_noise_stats* d_stats = device_alloc<rt4_noise_stats>(1);
+  RT4_CHECK(rt4_light_noise_device(r.ctx, s.d_light, s.w, s.w, s.h, s.tone(), o.noise_threshold, nullptr, d_q, s.w, nullptr,
+                                   d_stats, nullptr, err, sizeof err));
+  HIP_CHECK(hipDeviceSynchronize());
+  const rt4_noise_stats ns = device_read<rt4_noise_stats>(d_stats, 1)[0];
+  if (o.noise_map) {
+    std::vector<float> qv = device_read<float>(d_q, npx);
+    for (float& v : qv)  // the writers clamp to [0, 1]: an unmeasured pixel (+inf) is white; NaN black
+      if (std::isnan(v)) v = 0.0f;
+    write_image(o, s.name, "_q", grey_image(qv).data(), 0, RT4_FRAME_RGBA32F, s.w, s.h, false, ", display error q");
+    (void)hipFree(d_q);
+  }
+  (void)hipFree(d_stats);
+  std::printf("noise %s: pixels %llu, measured %llu, above %llu (threshold %.6g), max_q %.6g, max_se %.6g\n", s.name,
+              static_cast<unsigned long long>(ns.pixels), static_cast<unsigned long long>(ns.measured),
+              static_cast<unsigned long long>(ns.above), static_cast<double>(o.noise_threshold),
+              static_cast<double>(ns.max_q), static_cast<double>(ns.max_se));
+  if (!o.adaptive) return;
+  std::vector<int32_t> sorted(npx);
+  for (size_t p = 0; p < npx; p++) sorted[p] = acc[p].n;
+  std::sort(sorted.begin(), sorted.end());
+  const int32_t n_max = sorted.back();
+  std::vector<float> share(npx);
+  for (size_t p = 0; p < npx; p++) share[p] = n_max > 0 ? static_cast<float>(acc[p].n) / static_cast<float>(n_max) : 0.0f;
+  write_image(o, s.name, "_n", grey_image(share).data(), 0, RT4_FRAME_RGBA32F, s.w, s.h, false, ", frames per pixel");
+  std::printf("adaptive %s: n min %d, median %d, max %d\n", s.name, sorted.front(), sorted[npx / 2], n_max);
+}
+
+// Step 4, one section: its image; next to it the filtered frame and the window image (which share d_gbuf and d_dn);
+// the light path's statistics, maps and checkpoint; from the main section --checkpoint.
+void write_section_outputs(const Options& o, Run& r, const Section& s) {
+  const std::vector<unsigned char> host = device_read<unsigned char>(s.d_frame, s.frame_bytes(o.px()));
+  write_image(o, s.name, "", host.data(), host.size(), o.format, s.w, s.h, true, "");
+  rt4_gbuffer_px* d_gbuf = nullptr;  // the G-buffer of the last pose and the filtered frame
+  void* d_dn = nullptr;
+  if ((o.denoise_levels > 0 || o.light_denoise_levels >= 0) && o.frames >= 1) filtered_frame(o, r, s, d_gbuf, d_dn);
+  if (o.window_scale != 0 && o.frames >= 1) window_image(o, r, s, d_gbuf, d_dn);
+  if (d_gbuf) (void)hipFree(d_gbuf);
+  if (d_dn) (void)hipFree(d_dn);
+  if (o.light) light_outputs(o, r, s);
+  if (s.id == RT4_SECTION_YXZ && !o.checkpoint_path.empty()) {
+    // frames_done counts camera-resting frames only: a moving camera restarts the blend (frame_number 1)
+    const long long rested = static_cast<long long>(r.cam.frame_number) - 1;
+    RT4_CHECK(rt4_accum_save_key(o.checkpoint_path.c_str(), host.data(), o.format, s.w, s.h, s.w, rested, o.seed, r.run_key, err,
+                                 sizeof err));
+    std::printf("checkpoint %s (%lld frames)\n", o.checkpoint_path.c_str(), rested);
+  }
+}
+
+// Step 5 on one GPU: the summary, and the device state released.
+void close_render(const Options& o, Run& r) {
+  if (o.pool())
+    std::printf("pooled %zu light checkpoints, images 1\n", o.light_pool.size());
+  else
+    print_summary(o.light_gpus > 0 ? "light gpus " + std::to_string(o.light_gpus) + " (" + o.light_split + "), " : "", o.frames,
+                  r.sections.size(), r.count, r.ms / o.frames, r.ms);
+  for (Section& s : r.sections) {
+    rt4_temporal_destroy(s.temporal);
+    if (s.d_light) (void)hipFree(s.d_light);
+    (void)hipFree(s.d_frame);
+  }
+  (void)hipFree(r.d_count);
+  rt4_context_destroy(r.ctx);
+}
+
+}  // namespace
+
+// The steps: options, refusals, inputs, then either the --gpus run or, on one GPU, device state,
+// frames, every section's outputs and the summary.
+int main(int argc, char** argv) {
+  // The frame loop's overlapped launches of small frames use up to 8 side streams (DESIGN.md §4.28): give the
+  // process 8 hardware queues unless the environment says otherwise (read when the HIP runtime starts).
+  setenv("GPU_MAX_HW_QUEUES", "8", 0);
+  const Options o = parse_args(argc, argv);
+  refuse_conflicts(o);
+  const ShardHooks hooks = shard_hooks(o.rehearse);
+  Run r = load_inputs(o);
+  if (o.light_gpus > 0 && !o.rehearse) need_devices("--light-gpus", o.light_gpus);
+  window_scales(o, r);
+  if (o.gpus > 0 && !o.rehearse) need_devices("--gpus", o.gpus);
+  if (o.gpus > 0) {
+    run_bands(o, hooks, r);
+  } else {
+    open_render(o, r);
+    if (o.pipelined()) pipelined_frames(o, r);
+    if (o.light) open_light(o, r);
+    render_frames(o, hooks, r);
+    for (const Section& s : r.sections) write_section_outputs(o, r, s);
+    close_render(o, r);
+  }
+  rt4_properties_free(r.props);
+  std::free(r.scene);
   return 0;
 }
+
