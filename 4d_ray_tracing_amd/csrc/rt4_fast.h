@@ -190,12 +190,19 @@ __device__ __forceinline__ Cand cyl_cand(const CylProj& p, V4 cp, float r, const
 __device__ __forceinline__ bool sphere_culled(float d2, float dp, float d2_out, float r2m) {
   return d2 >= d2_out && (dp < 0.0f || d2 - dp * dp > fmaf_(SPHERE_CULL_K, d2, r2m));
 }
+// PROBE (rt4_debug_cull only): also writes the cull's decision to *probe, 1 = the exact part was skipped by
+// sphere_culled, 0 otherwise (a projection that misses included). A compile-time branch, as in hypercube_cand.
+template <bool PROBE = false>
 __device__ __forceinline__ Cand cyl_cand_cull(const CylProj& p, V4 cp, float r, const DivC& dc, const SphereCull& k,
-                                              bool outer, uint32_t id) {
+                                              bool outer, uint32_t id, uint32_t* probe = nullptr) {
+  if constexpr (PROBE) *probe = 0u;
   if (p.miss) return no_cand();
   const V4 po = sub(cp, p.r12.point);
   const float d2 = dot(po, po), dp = dot(po, p.r12.drct);
-  if (sphere_culled(d2, dp, k.d2_out, k.r2m)) return no_cand();
+  if (sphere_culled(d2, dp, k.d2_out, k.r2m)) {
+    if constexpr (PROBE) *probe = 1u;
+    return no_cand();
+  }
   Cand c = sphere_cand_d(d2, dp, r, dc, outer, id);
   c.dist = c.dist / p.len;  // inter.dist /= drct_in_plane_length (:265)
   return c;

@@ -1430,6 +1430,42 @@ __global__ void rt4_bound_skip_kernel(const rt4_scene_desc* __restrict__ S, cons
   out[t] = m;
 }
 
+// The sphere cull's decisions of n rays, one lane each (rt4_debug_cull, rt4.h for the bits): find_pre's pending
+// mask in its runtime-count form (every sphere of the scene), and cyl_cand_cull's own decision (its PROBE branch)
+// for every cylinder and every union's two cylinders, called as find_rest and union_cand call it. rays: n x 8
+// floats, out: n x 2 words.
+__global__ void rt4_cull_kernel(const rt4_scene_desc* __restrict__ S, const SceneAux* __restrict__ X,
+                                const float* __restrict__ rays, uint32_t* __restrict__ out, int64_t n) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const float* r = rays + 8 * t;
+  const Ray ray{ld4(r), ld4(r + 4)};
+  uint32_t pend = 0;
+  (void)find_pre<K_SPHERES>(S, X, ray, pend);
+  const uint32_t all = S->n_spheres >= 32 ? 0xFFFFFFFFu : (1u << S->n_spheres) - 1u;
+  uint32_t m = 0;
+  for (int i = 0; i < S->n_cylinders; i++) {
+    const rt4_cylinder& c = S->cylinders[i];
+    const V4 cp = ld4(c.point);
+    uint32_t culled = 0;
+    (void)cyl_cand_cull<true>(cyl_project(cp, ld4(c.axis1), ld4(c.axis2), ray), cp, c.r, X->cyl_r[i], X->cyl_cull[i], true,
+                              0u, &culled);
+    m |= culled << i;
+  }
+  for (int i = 0; i < S->n_unions; i++) {
+    const rt4_cylinders_union& u = S->unions[i];
+    const V4 p1 = ld4(u.cylinder1.point), p2 = ld4(u.cylinder2.point);
+    uint32_t c1 = 0, c2 = 0;
+    (void)cyl_cand_cull<true>(cyl_project(p1, ld4(u.cylinder1.axis1), ld4(u.cylinder1.axis2), ray), p1, u.cylinder1.r,
+                              X->union_r[i][0], X->union_cull[i][0], true, 0u, &c1);
+    (void)cyl_cand_cull<true>(cyl_project(p2, ld4(u.cylinder2.axis1), ld4(u.cylinder2.axis2), ray), p2, u.cylinder2.r,
+                              X->union_r[i][1], X->union_cull[i][1], true, 0u, &c2);
+    m |= (c1 | (c2 << 1)) << (16 + 2 * i);
+  }
+  out[2 * t] = ~pend & all;
+  out[2 * t + 1] = m;
+}
+
 // Tile order for the pixel queue (longest work first): one thread per 8x8 tile traces the primary ray
 // of the tile's centre pixel; tiles whose ray hits something go to the front of `order`, sky tiles to
 // the back. The queue hands tiles out in this order, so the slow tiles do not form the drain at the
@@ -2994,6 +3030,25 @@ int rt4_debug_bound_skip(rt4_context* ctx, const float* rays, uint32_t* out_mask
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = dout.down(out_mask);
   if (e != hipSuccess) return rt4_set_err(err, errlen, "debug_bound_skip failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
+  return RT4_OK;
+}
+
+int rt4_debug_cull(rt4_context* ctx, const float* rays, uint32_t* out, int64_t n, char* err, size_t errlen) {
+  if (!ctx || !rays || !out || n < 0) return rt4_set_err(err, errlen, "bad argument"), RT4_ERR_ARG;
+  if (!ctx->has_scene) return rt4_set_err(err, errlen, "context has no scene"), RT4_ERR_ARG;
+  if (n == 0) return RT4_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HostStage dr, dout;
+  hipError_t e = dr.up(rays, n * 8 * sizeof(float));
+  if (e == hipSuccess) e = dout.up(nullptr, n * 2 * sizeof(uint32_t));
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(rt4_cull_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, 0, ctx->d_scene,
+                       scene_aux(ctx), dr.as<float>(), dout.as<uint32_t>(), n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = dout.down(out);
+  if (e != hipSuccess) return rt4_set_err(err, errlen, "debug_cull failed: %s", hipGetErrorString(e)), RT4_ERR_HIP;
   return RT4_OK;
 }
 

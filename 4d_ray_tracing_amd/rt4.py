@@ -250,6 +250,7 @@ def _load(path=None):
         "rt4_debug_find_intersection": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
         "rt4_debug_final_light": ([c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
         "rt4_debug_bound_skip": ([c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
+        "rt4_debug_cull": ([c_void_p, c_void_p, c_void_p, c_int64] + E, c_int),
         "rt4_debug_sqrt_thresholds": ([c_float, POINTER(c_float), POINTER(c_float)], c_int),
         "rt4_context_kernel_shape": ([c_void_p], c_uint32),
         "rt4_debug_verify_sqrt": ([c_void_p, POINTER(c_uint64)] + E, c_int),
@@ -406,7 +407,7 @@ EXPORTED = (
     "rt4_accum_save_key rt4_accum_key rt4_accum_key_of "
     "rt4_scene_surface_count rt4_scene_surface rt4_render_gbuffer_device rt4_render_gbuffer_host "
     "rt4_denoise_params_default rt4_denoise_device rt4_denoise_host rt4_context_denoise_bytes "
-    "rt4_debug_final_light rt4_debug_bound_skip rt4_debug_sqrt_thresholds "
+    "rt4_debug_final_light rt4_debug_bound_skip rt4_debug_cull rt4_debug_sqrt_thresholds "
     "rt4_reproject_params_default rt4_reproject_device rt4_reproject_host rt4_temporal_blend_device rt4_temporal_create "
     "rt4_temporal_destroy rt4_temporal_reset rt4_temporal_frame_device rt4_temporal_image rt4_temporal_history "
     "rt4_temporal_gbuffer rt4_temporal_read_host rt4_temporal_bytes "
@@ -1511,6 +1512,19 @@ class Tracer:
         err = _errbuf()
         _check(self._lib.rt4_debug_bound_skip(self._h, c_void_p(rays.ctypes.data), c_void_p(out.ctypes.data),
                                               rays.shape[0], err, len(err)), err)
+        return out
+
+    def debug_cull(self, rays):
+        """The trace kernels' sphere-cull decisions for rays (n, 8) (rt4_debug_cull): (n, 2) uint32, word 0 bit i
+        sphere i not pending after the cull pass, word 1 bit i cylinder i culled, bit 16 + 2u + c union u's
+        cylinder c culled."""
+        import numpy as np
+
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        out = np.empty((rays.shape[0], 2), np.uint32)
+        err = _errbuf()
+        _check(self._lib.rt4_debug_cull(self._h, c_void_p(rays.ctypes.data), c_void_p(out.ctypes.data),
+                                        rays.shape[0], err, len(err)), err)
         return out
 
 

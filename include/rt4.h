@@ -1036,6 +1036,18 @@ int rt4_debug_final_light(rt4_context* ctx, const float* drct, float* out, int64
  * Synchronous; host buffers. RT4_ERR_ARG (nothing written) for a NULL pointer, n < 0 or a context without a scene. */
 int rt4_debug_bound_skip(rt4_context* ctx, const float* rays, uint32_t* out_mask, int64_t n, char* err, size_t errlen);
 
+/* The trace kernels' sphere-cull decisions (their own device functions, on the context's scene and its constants) for
+ * n rays, one lane each. rays: n x 8 floats (point xyzw, drct xyzw), as they are. out: two uint32 per ray:
+ *   word 0, bit i           sphere i is not pending after the cull pass: its exact test is skipped (the ray starts
+ *                           outside and points away, or its line clears the sphere by the cull's margin),
+ *   word 1, bit i (i < 16)  cylinder i's exact part is skipped by the same cull on the projected ray (0 for a ray
+ *                           whose projection onto the cylinder's plane misses before the cull is asked),
+ *   word 1, bit 16 + 2u + c the same for cylinder c (0 / 1) of union u.
+ * An object that the scene lacks gives 0; so does a cull the host disabled, but for the spheres' early-out of rays
+ * that point away, which needs none of the host's margin. The mask is the same under either kernel flag.
+ * Synchronous; host buffers. RT4_ERR_ARG (nothing written) for a NULL pointer, n < 0 or a context without a scene. */
+int rt4_debug_cull(rt4_context* ctx, const float* rays, uint32_t* out, int64_t n, char* err, size_t errlen);
+
 /* The thresholds rt4_context_set_scene makes from a radius r for the band filters of the union and the tiger, which
  * compare the squared distance q to the other axes pair without a square root: for every float q that dot(v, v) can
  * give (+0, denormals, normals, +inf, NaN)
