@@ -885,6 +885,70 @@ int rt4_progressive_uniforms(const rt4_uniforms* base, uint32_t frame_number, rt
   return RT4_OK;
 }
 
+// ---- 3D retina view: the host-only parts (rt4.h; the passes are rt4_retina.h's)
+int rt4_retina_slice_uniforms(const rt4_uniforms* u, const float w_drct[4], int32_t depth, float depth_size,
+                              int32_t slice, rt4_uniforms* out) {
+  if (!u || !w_drct || !out) return RT4_ERR_ARG;
+  if (depth < 1 || depth > RT4_RETINA_MAX_DEPTH || slice < 0 || slice >= depth) return RT4_ERR_ARG;
+  if (!(depth_size > 0.0f) || !std::isfinite(depth_size)) return RT4_ERR_ARG;
+  const float t = ((static_cast<float>(slice) + 0.5f) / static_cast<float>(depth) - 0.5f) * depth_size;
+  rt4_uniforms s = *u;
+  if (t != 0.0f)
+    for (int c = 0; c < 4; c++) s.vec_to_mtr[c] = std::fmaf(w_drct[c], t, u->vec_to_mtr[c]);
+  s.seed = static_cast<int32_t>(static_cast<uint32_t>(u->seed) + static_cast<uint32_t>(slice - depth / 2) * 0x85EBCA6Bu);
+  *out = s;
+  return RT4_OK;
+}
+
+void rt4_retina_params_default(rt4_retina_params* p) {
+  if (!p) return;
+  p->alpha_sky = 0.0f;
+  p->alpha_fill = 1.0f / 32.0f;
+  p->alpha_edge = 0.5f;
+  p->t_min = 1.0f / 256.0f;
+  p->background[0] = p->background[1] = p->background[2] = 0.0f;
+}
+
+int rt4_retina_view_make(int32_t w, int32_t h, int32_t d, const float size[3], float yaw, float pitch, float extent,
+                         int32_t ow, int32_t oh, float step_voxels, rt4_retina_view* view, char* err, size_t errlen) {
+  if (!size || !view) return rt4_set_err(err, errlen, "NULL argument"), RT4_ERR_ARG;
+  if (w < 1 || h < 1 || d < 1 || ow < 1 || oh < 1)
+    return rt4_set_err(err, errlen, "retina view: volume %d x %d x %d and picture %d x %d must be >= 1", w, h, d, ow, oh),
+           RT4_ERR_ARG;
+  for (int c = 0; c < 3; c++)
+    if (!(size[c] > 0.0f) || !std::isfinite(size[c]))
+      return rt4_set_err(err, errlen, "retina view: size[%d] must be finite and > 0", c), RT4_ERR_ARG;
+  if (!std::isfinite(yaw) || !std::isfinite(pitch) || !std::isfinite(extent) || !(extent >= 0.0f) ||
+      !std::isfinite(step_voxels) || !(step_voxels > 0.0f))
+    return rt4_set_err(err, errlen, "retina view: angles finite, extent finite and >= 0, step_voxels finite and > 0"), RT4_ERR_ARG;
+  const double S[3] = {size[0], size[1], size[2]};
+  const double cy = std::cos(static_cast<double>(yaw)), sy = std::sin(static_cast<double>(yaw));
+  const double cp = std::cos(static_cast<double>(pitch)), sp = std::sin(static_cast<double>(pitch));
+  const double F0[3] = {sy, 0.0, cy}, R[3] = {cy, 0.0, -sy};
+  const double F[3] = {cp * F0[0], -sp, cp * F0[2]};
+  const double U[3] = {sp * F0[0], cp, sp * F0[2]};
+  const double ext = extent > 0.0f ? static_cast<double>(extent) : std::sqrt(S[0] * S[0] + S[1] * S[1] + S[2] * S[2]);
+  const double ext_v = ext * static_cast<double>(oh) / static_cast<double>(ow);
+  const double e = 0.5 * (std::fabs(F[0]) * S[0] + std::fabs(F[1]) * S[1] + std::fabs(F[2]) * S[2]);
+  const double step = static_cast<double>(step_voxels) * std::min(S[0] / w, std::min(S[1] / h, S[2] / d));
+  // less 1/1024 of a step: an angle that is a right angle but for its float rounding adds no step
+  const double n_steps = std::ceil(2.0 * e / step - 1.0 / 1024.0);
+  if (!(n_steps <= static_cast<double>(RT4_RETINA_MAX_STEPS)))
+    return rt4_set_err(err, errlen, "retina view: %.0f steps, more than %d (a larger step_voxels)", n_steps, RT4_RETINA_MAX_STEPS),
+           RT4_ERR_ARG;
+  // scene -> voxel: a scale and an offset per axis
+  const double scale[3] = {w / S[0], -static_cast<double>(h) / S[1], d / S[2]};
+  const double offset[3] = {0.5 * w - 0.5, 0.5 * h - 0.5, 0.5 * d - 0.5};
+  for (int c = 0; c < 3; c++) {
+    view->origin[c] = static_cast<float>(scale[c] * (-e * F[c]) + offset[c]);
+    view->du[c] = static_cast<float>(scale[c] * (ext * R[c]));
+    view->dv[c] = static_cast<float>(scale[c] * (ext_v * U[c]));
+    view->dt[c] = static_cast<float>(scale[c] * (step * F[c]));
+  }
+  view->steps = std::max(1, static_cast<int32_t>(n_steps));
+  return RT4_OK;
+}
+
 // ---- surface index: the order of the kernel's flat primitive table (rt4_trace.hip build_aux)
 int32_t rt4_scene_surface_count(const rt4_scene_desc* s) {
   if (!s) return 0;

@@ -71,6 +71,15 @@
 //                   empty selection, is a whole-frame pass; the loop never stops early. One line per pass, the min /
 //                   median / max of n at the end, and <prefix>_<section>_n.<ext>: n over the largest n as grey.
 //                   Defaults 8, 4, 4, 4, 1: the values of the study in DESIGN.md §4.39)
+//                   [--retina D [--retina-size X] [--retina-view YAW PITCH] [--retina-turntable N] [--retina-step S]]
+//                   (the 3D retina view, DESIGN.md §4.47: the -n frames go into a D-slice light volume of the section's
+//                   view, the slices spread over X scene units along the camera's w axis (default: the matrix height),
+//                   rt4_retina_accumulate_device; the volume is projected, rt4_retina_present_device, to
+//                   <prefix>_yxz_retina.<ext> at the window's pixel size (cells * the main window's cell_size), seen
+//                   from YAW PITCH degrees (default 30 20), S voxels per sample (default 1). --retina-turntable N: instead
+//                   N pictures <prefix>_yxz_retina_000 .. at yaw 360 k / N, all from the one accumulated volume. One
+//                   section, one GPU, a resting camera; --light is implied. Not with -3, --gpus, --light-gpus,
+//                   --reproject, --adaptive, --denoise, --light-denoise, --window, --frame-by-frame, nor any checkpoint flag)
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -479,6 +488,10 @@ struct Options {
   int ad_warmup = 8, ad_pass = 4, ad_full_every = 4;  // --adaptive-warmup / --adaptive-pass / --adaptive-full-every
   // --adaptive-min-above / --adaptive-dilate; threshold: --noise-threshold
   rt4_tile_select_params ad_select = defaults(rt4_tile_select_params_default);
+  // --retina D: 0 = off; the --retina-* flags: size 0 = the matrix height, the view in degrees
+  int retina_depth = 0, retina_turntable = 0;
+  bool retina = false, retina_given = false;
+  float retina_size = 0.0f, retina_yaw = 30.0f, retina_pitch = 20.0f, retina_step = 1.0f;
 
   bool pool() const { return !light_pool.empty(); }
   bool moving() const { return keys && move_seconds > 0.0f; }
@@ -540,6 +553,14 @@ Options parse_args(int argc, char** argv) {
     else if (a == "--adaptive-full-every") o.ad_full_every = std::atoi(next()), o.ad_given = true;
     else if (a == "--adaptive-min-above") o.ad_select.min_above = std::atoi(next()), o.ad_given = true;
     else if (a == "--adaptive-dilate") o.ad_select.dilate = std::atoi(next()), o.ad_given = true;
+    else if (a == "--retina") o.retina_depth = std::atoi(next()), o.retina = true;
+    else if (a == "--retina-size") o.retina_size = static_cast<float>(std::atof(next())), o.retina_given = true;
+    else if (a == "--retina-view") {
+      o.retina_yaw = static_cast<float>(std::atof(next()));
+      o.retina_pitch = static_cast<float>(std::atof(next()));
+      o.retina_given = true;
+    } else if (a == "--retina-turntable") o.retina_turntable = std::atoi(next()), o.retina_given = true;
+    else if (a == "--retina-step") o.retina_step = static_cast<float>(std::atof(next())), o.retina_given = true;
     else if (a == "--window-nearest") o.window_nearest = true, o.window_scale = o.window_scale ? o.window_scale : -1;
     else if (a == "--window") {
       o.window_scale = optional_number(argc, argv, i, -1);
@@ -559,11 +580,36 @@ Options parse_args(int argc, char** argv) {
   return o;
 }
 
+// --retina and its flags, ahead of every other refusal (a command line without them passes straight through): the
+// volume is one section's light accumulation on one GPU with a resting camera, and it writes projections only.
+void refuse_retina_conflicts(const Options& o) {
+  const char* f = "--retina";
+  if (o.retina_given && !o.retina) die(f, "--retina-size / --retina-view / --retina-turntable / --retina-step need --retina D");
+  if (!o.retina) return;
+  if (o.retina_depth < 1 || o.retina_depth > RT4_RETINA_MAX_DEPTH) die(f, "D must be 1..256 slices");
+  if (o.gpus > 0 || o.light_gpus != 0) die(f, "not with --gpus / --light-gpus: the volume is accumulated on one GPU");
+  if (o.three) die(f, "not with -3: the volume holds the main section's view");
+  if (o.reproject) die(f, "not with --reproject: the volume is a light accumulation of one view");
+  if (o.adaptive || o.ad_given) die(f, "not with --adaptive: every slice takes every frame");
+  if (o.denoise_levels > 0 || o.light_denoise_levels >= 0) die(f, "not with --denoise / --light-denoise: the projection is not filtered");
+  if (o.window_scale != 0) die(f, "not with --window: the projection is written at the window's size already");
+  if (o.checkpoints() || !o.light_resume_path.empty() || !o.light_checkpoint_path.empty() || o.pool())
+    die(f, "not with --resume / --checkpoint / --light-resume / --light-checkpoint / --light-pool: no file format holds a volume");
+  if (o.frame_by_frame) die(f, "not with --frame-by-frame: the frames go through rt4_render_light_device");
+  if (o.moving()) die(f, "needs a resting camera: the volume accumulates one view");
+  if (o.frames < 1) die(f, "frames must be >= 1");
+  if (o.retina_given && (!(o.retina_size >= 0.0f) || !std::isfinite(o.retina_size) || !std::isfinite(o.retina_yaw) ||
+                         !std::isfinite(o.retina_pitch) || o.retina_turntable < 0 || !(o.retina_step > 0.0f) ||
+                         !std::isfinite(o.retina_step)))
+    die(f, "size >= 0 (0: the matrix height), a view of two angles in degrees, turntable >= 0, step > 0");
+}
+
 // Every combination of flags that is refused whatever the files hold, in one place: the first check that fails is the
 // one reported, so the order below is part of the program's behaviour (tests/test_render_cli_refusals.py pins it).
 // What depends on a file's contents (a checkpoint's seed, key, size, pooled flag; the 2^32 frame bound) is refused by
 // load_inputs, and a missing device by need_devices, after this.
 void refuse_conflicts(const Options& o) {
+  refuse_retina_conflicts(o);
   if (o.reproject && o.gpus > 0) die("--reproject", "not with --gpus: the temporal image lives on one GPU");
   if (o.reproject && o.checkpoints())
     die("--reproject", "not with --resume / --checkpoint: a checkpoint holds no per-pixel history");
@@ -1135,6 +1181,58 @@ void write_section_outputs(const Options& o, Run& r, const Section& s) {
   }
 }
 
+// --retina: the whole run on one GPU. The -n frames into the D-slice volume of the main section's view, then one
+// projection per picture: every picture after the first costs no tracing.
+void run_retina(const Options& o, Run& r) {
+  const Section& s = r.sections[0];
+  int32_t scale = 1;
+  RT4_CHECK(rt4_properties_get_int(r.props, "window.main.cell_size", &scale, err, sizeof err));
+  if (scale < 1 || s.w > 65535 / scale || s.h > 65535 / scale) die("--retina", "the window's pixel size is not in [1, 65535]");
+  const int32_t ow = s.w * scale, oh = s.h * scale;
+  rt4_uniforms u;
+  RT4_CHECK(rt4_camera_frame_uniforms(&r.cam, &s.base, s.id, static_cast<int32_t>(o.seed), &u));
+  const float depth_size = o.retina_size > 0.0f ? o.retina_size : u.mtr_sizes[1];
+  const float size[3] = {u.mtr_sizes[0], u.mtr_sizes[1], depth_size};
+  const float rad = 3.14159265358979323846f / 180.0f;
+  const int n_views = std::max(o.retina_turntable, 1);
+  std::vector<rt4_retina_view> views(static_cast<size_t>(n_views));
+  for (int v = 0; v < n_views; v++) {  // before any HIP call: a step too small for the box is refused here
+    const float yaw = o.retina_turntable > 0 ? 360.0f * static_cast<float>(v) / static_cast<float>(n_views) : o.retina_yaw;
+    RT4_CHECK(rt4_retina_view_make(s.w, s.h, o.retina_depth, size, yaw * rad, o.retina_pitch * rad, 0.0f, ow, oh, o.retina_step,
+                                   &views[static_cast<size_t>(v)], err, sizeof err));
+  }
+  RT4_CHECK(rt4_context_create(o.device, RT4_FLAG_SAMPLER_LUT, &r.ctx, err, sizeof err));
+  RT4_CHECK(rt4_context_set_scene(r.ctx, r.scene, err, sizeof err));
+  rt4_retina* ret = nullptr;
+  RT4_CHECK(rt4_retina_create(r.ctx, s.w, s.h, o.retina_depth, &ret, err, sizeof err));
+  r.d_count = device_alloc<unsigned long long>(1, true);
+  void* d_frame = device_alloc<unsigned char>(static_cast<size_t>(ow) * oh * o.px());
+  HIP_CHECK(hipEventCreate(&r.e0));
+  HIP_CHECK(hipEventCreate(&r.e1));
+  HIP_CHECK(hipEventRecord(r.e0, nullptr));
+  RT4_CHECK(rt4_retina_accumulate_device(ret, &u, r.cam.orientation.w_drct, depth_size, o.frames, r.d_count, nullptr, err, sizeof err));
+  HIP_CHECK(hipEventRecord(r.e1, nullptr));
+  HIP_CHECK(hipEventSynchronize(r.e1));
+  HIP_CHECK(hipEventElapsedTime(&r.ms, r.e0, r.e1));
+  HIP_CHECK(hipMemcpy(&r.count, r.d_count, sizeof r.count, hipMemcpyDeviceToHost));
+  for (int v = 0; v < n_views; v++) {
+    RT4_CHECK(rt4_retina_present_device(ret, &views[static_cast<size_t>(v)], nullptr, s.tone(), d_frame, o.format, ow, ow, oh,
+                                        nullptr, err, sizeof err));
+    HIP_CHECK(hipDeviceSynchronize());
+    const std::vector<unsigned char> host = device_read<unsigned char>(d_frame, static_cast<size_t>(ow) * oh * o.px());
+    char suffix[32] = "_retina";
+    if (o.retina_turntable > 0) std::snprintf(suffix, sizeof suffix, "_retina_%03d", v);
+    write_image(o, s.name, suffix, host.data(), host.size(), o.format, ow, oh, true,
+                ", " + std::to_string(o.retina_depth) + " slices, " + std::to_string(views[static_cast<size_t>(v)].steps) + " steps");
+  }
+  print_summary("retina " + std::to_string(o.retina_depth) + " slices, ", o.frames, static_cast<size_t>(n_views), r.count,
+                r.ms / o.frames, r.ms);
+  (void)hipFree(d_frame);
+  (void)hipFree(r.d_count);
+  rt4_retina_destroy(ret);
+  rt4_context_destroy(r.ctx);
+}
+
 // Step 5 on one GPU: the summary, and the device state released.
 void close_render(const Options& o, Run& r) {
   if (o.pool())
@@ -1166,7 +1264,9 @@ int main(int argc, char** argv) {
   if (o.light_gpus > 0 && !o.rehearse) need_devices("--light-gpus", o.light_gpus);
   window_scales(o, r);
   if (o.gpus > 0 && !o.rehearse) need_devices("--gpus", o.gpus);
-  if (o.gpus > 0) {
+  if (o.retina) {
+    run_retina(o, r);
+  } else if (o.gpus > 0) {
     run_bands(o, hooks, r);
   } else {
     open_render(o, r);

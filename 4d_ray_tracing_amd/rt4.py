@@ -193,6 +193,19 @@ LIGHT_MERGE_MAX = 16  # rt4.h RT4_LIGHT_MERGE_MAX
 LIGHT_POOLED = 0x1  # rt4.h RT4_LIGHT_POOLED: a light checkpoint of several seeds, not resumable
 
 
+class RetinaParams(Structure):  # rt4.h rt4_retina_params
+    _fields_ = [("alpha_sky", c_float), ("alpha_fill", c_float), ("alpha_edge", c_float), ("t_min", c_float),
+                ("background", c_float * 3)]
+
+
+class RetinaView(Structure):  # rt4.h rt4_retina_view: the picture's rays in voxel coordinates
+    _fields_ = [("origin", c_float * 3), ("du", c_float * 3), ("dv", c_float * 3), ("dt", c_float * 3), ("steps", c_int32)]
+
+
+RETINA_MAX_DEPTH = 256  # rt4.h RT4_RETINA_MAX_DEPTH
+RETINA_MAX_STEPS = 4096  # rt4.h RT4_RETINA_MAX_STEPS
+
+
 def _gbuffer_dtype():
     import numpy as np
 
@@ -375,6 +388,32 @@ def _load(path=None):
                             POINTER(c_uint32), POINTER(c_uint32)] + E, c_int),
         "rt4_light_load": ([c_char_p, c_void_p, c_int32, c_int32, c_int64, POINTER(c_int64), POINTER(c_uint32),
                             POINTER(c_uint32), POINTER(c_uint32)] + E, c_int),
+        "rt4_retina_slice_uniforms": ([POINTER(Uniforms), POINTER(c_float), c_int32, c_float, c_int32, POINTER(Uniforms)], c_int),
+        "rt4_retina_params_default": ([POINTER(RetinaParams)], None),
+        "rt4_retina_view_make": ([c_int32, c_int32, c_int32, POINTER(c_float), c_float, c_float, c_float, c_int32, c_int32,
+                                  c_float, POINTER(RetinaView)] + E, c_int),
+        "rt4_retina_voxelize_device": ([c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_float,
+                                        POINTER(RetinaParams), c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
+                                        c_void_p] + E, c_int),
+        "rt4_retina_voxelize_host": ([c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_float,
+                                      POINTER(RetinaParams), c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32] + E, c_int),
+        "rt4_retina_project_device": ([c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(RetinaView),
+                                       POINTER(RetinaParams), c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p] + E, c_int),
+        "rt4_retina_project_host": ([c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(RetinaView),
+                                     POINTER(RetinaParams), c_void_p, c_int32, c_int64, c_int32, c_int32] + E, c_int),
+        "rt4_retina_create": ([c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)] + E, c_int),
+        "rt4_retina_destroy": ([c_void_p], None),
+        "rt4_retina_reset": ([c_void_p], None),
+        "rt4_retina_accumulate_device": ([c_void_p, POINTER(Uniforms), POINTER(c_float), c_float, c_int32, c_void_p,
+                                          c_void_p] + E, c_int),
+        "rt4_retina_present_device": ([c_void_p, POINTER(RetinaView), POINTER(RetinaParams), c_float, c_void_p, c_int32,
+                                       c_int64, c_int32, c_int32, c_void_p] + E, c_int),
+        "rt4_retina_frames_done": ([c_void_p], c_int64),
+        "rt4_retina_light": ([c_void_p], c_void_p),
+        "rt4_retina_gbuffer": ([c_void_p], c_void_p),
+        "rt4_retina_voxels": ([c_void_p], c_void_p),
+        "rt4_retina_read_host": ([c_void_p, c_void_p, c_void_p, c_void_p] + E, c_int),
+        "rt4_retina_bytes": ([c_void_p], c_uint64),
     }
     tolerant = os.environ.get("RT4_AB_TOLERANT") == "1"  # tools/abtest.sh: older builds lack newer exports
     for name, (argtypes, restype) in sig.items():
@@ -420,7 +459,11 @@ EXPORTED = (
     "rt4_tile_select_params_default rt4_light_select_tiles_device rt4_light_select_tiles_host "
     "rt4_render_light_tiles_device rt4_render_light_tiles_host rt4_context_select_bytes "
     "rt4_light_merge_device rt4_light_merge_host rt4_light_bands_unpermute_device rt4_frame_split "
-    "rt4_light_save rt4_light_info rt4_light_load"
+    "rt4_light_save rt4_light_info rt4_light_load "
+    "rt4_retina_slice_uniforms rt4_retina_params_default rt4_retina_view_make rt4_retina_voxelize_device "
+    "rt4_retina_voxelize_host rt4_retina_project_device rt4_retina_project_host rt4_retina_create rt4_retina_destroy "
+    "rt4_retina_reset rt4_retina_accumulate_device rt4_retina_present_device rt4_retina_frames_done rt4_retina_light "
+    "rt4_retina_gbuffer rt4_retina_voxels rt4_retina_read_host rt4_retina_bytes"
 ).split()
 
 if ctypes.sizeof(SceneDesc) != lib.rt4_scene_desc_size() or ctypes.sizeof(Uniforms) != lib.rt4_uniforms_size():
@@ -679,6 +722,43 @@ def upscale_uniforms(u_cells: Uniforms, scale: int) -> Uniforms:
     if st != 0:
         raise RT4Error(st, f"scale {scale} outside 1..{UPSCALE_MAX_SCALE}, or a window beyond 65535 x 16383")
     return out
+
+
+def retina_params(alpha_sky: float | None = None, alpha_fill: float | None = None, alpha_edge: float | None = None,
+                  t_min: float | None = None, background=None) -> RetinaParams:
+    """rt4_retina_params: the library's defaults, overridden by the arguments given."""
+    p = RetinaParams()
+    lib.rt4_retina_params_default(byref(p))
+    for name, v in (("alpha_sky", alpha_sky), ("alpha_fill", alpha_fill), ("alpha_edge", alpha_edge), ("t_min", t_min)):
+        if v is not None:
+            setattr(p, name, v)
+    if background is not None:
+        p.background[0], p.background[1], p.background[2] = background
+    return p
+
+
+def retina_slice_uniforms(u: Uniforms, w_drct, depth: int, depth_size: float, slice_index: int) -> Uniforms:
+    """The uniforms of one slice of a `depth`-slice retina of the view u (rt4_retina_slice_uniforms): the matrix centre
+    shifted along w_drct, the seed decorrelated; the middle slice of an odd depth is u itself."""
+    out = Uniforms()
+    wd = (c_float * 4)(*w_drct)
+    if lib.rt4_retina_slice_uniforms(byref(u), wd, depth, depth_size, slice_index, byref(out)) != 0:
+        raise RT4Error(-1, f"retina_slice_uniforms: depth {depth}, slice {slice_index}, depth_size {depth_size}")
+    return out
+
+
+def retina_view(w: int, h: int, d: int, size, yaw: float = 0.0, pitch: float = 0.0, extent: float = 0.0, ow: int = 0,
+                oh: int = 0, step_voxels: float = 1.0) -> RetinaView:
+    """An orthographic view of the w x h x d retina box of `size` scene units (mtr_sizes[0], mtr_sizes[1], depth_size)
+    for an ow x oh picture (rt4_retina_view_make); angles in radians, extent 0 = the box diagonal."""
+    v = RetinaView()
+    sz = (c_float * 3)(*size)
+    err = _errbuf()
+    _check(lib.rt4_retina_view_make(w, h, d, sz, yaw, pitch, extent, ow, oh, step_voxels, byref(v), err, len(err)), err)
+    return v
+
+
+VOXEL_DTYPE = "float32"  # a voxel volume: (d, h, row stride, 4) of premultiplied r, g, b, a
 
 
 def region(w: int, h: int, x0: int = 0, y0: int = 0, band_rows: int = 0, band_step: int = 0) -> Region:
@@ -1436,6 +1516,72 @@ class Tracer:
             log.append((kind, listed, n))
         return light, count, log
 
+    def retina_voxelize_device(self, light_ptr: int, light_strides, gbuf_ptr: int, gbuf_strides, k: float,
+                               params: RetinaParams | None, vox_ptr: int, vox_strides, w: int, h: int, d: int,
+                               stream: int = 0) -> None:
+        """Asynchronous: the premultiplied float4 voxel volume of a device light volume and G-buffer volume
+        (rt4_retina_voxelize_device); every *_strides is (row stride, slice stride) in elements."""
+        p = params if params is not None else retina_params()
+        err = _errbuf()
+        _check(self._lib.rt4_retina_voxelize_device(
+            self._h, c_void_p(light_ptr or None), light_strides[0], light_strides[1], c_void_p(gbuf_ptr or None),
+            gbuf_strides[0], gbuf_strides[1], k, byref(p), c_void_p(vox_ptr or None), vox_strides[0], vox_strides[1], w, h, d,
+            c_void_p(stream or None), err, len(err)), err)
+
+    def retina_voxelize_host(self, light, gbuf, k: float, params: RetinaParams | None = None, out=None, w: int | None = None,
+                             h: int | None = None):
+        """Synchronous: light (d, rows, stride) of LIGHT_DTYPE and gbuf (d, rows, stride) of GBUFFER_DTYPE into `out`
+        (d, rows, stride, 4) float32 (a new array if None). w, h: the slice size when rows or slices are padded."""
+        import numpy as np
+
+        assert light.dtype == LIGHT_DTYPE and gbuf.dtype == GBUFFER_DTYPE and light.ndim == 3 and gbuf.ndim == 3
+        d = light.shape[0]
+        h = light.shape[1] if h is None else h
+        w = light.shape[2] if w is None else w
+        if out is None:
+            out = np.zeros((d, h, w, 4), np.float32)
+        for a in (light, gbuf, out):
+            assert a.flags["C_CONTIGUOUS"] and a.shape[0] == d
+        assert out.dtype == np.float32 and out.ndim == 4 and out.shape[3] == 4
+        p = params if params is not None else retina_params()
+        err = _errbuf()
+        _check(self._lib.rt4_retina_voxelize_host(
+            self._h, c_void_p(light.ctypes.data), light.shape[2], light.shape[1] * light.shape[2], c_void_p(gbuf.ctypes.data),
+            gbuf.shape[2], gbuf.shape[1] * gbuf.shape[2], k, byref(p), c_void_p(out.ctypes.data), out.shape[2],
+            out.shape[1] * out.shape[2], w, h, d, err, len(err)), err)
+        return out
+
+    def retina_project_device(self, vox_ptr: int, vox_strides, w: int, h: int, d: int, view: RetinaView,
+                              params: RetinaParams | None, frame_ptr: int, fmt: int, frame_stride: int, ow: int, oh: int,
+                              stream: int = 0) -> None:
+        """Asynchronous: the ow x oh picture of `view` in `fmt` from a device voxel volume (rt4_retina_project_device)."""
+        p = params if params is not None else retina_params()
+        err = _errbuf()
+        _check(self._lib.rt4_retina_project_device(
+            self._h, c_void_p(vox_ptr or None), vox_strides[0], vox_strides[1], w, h, d,
+            byref(view) if view is not None else None, byref(p), c_void_p(frame_ptr or None), fmt, frame_stride, ow, oh,
+            c_void_p(stream or None), err, len(err)), err)
+
+    def retina_project_host(self, voxels, view: RetinaView, ow: int, oh: int, params: RetinaParams | None = None,
+                            fmt: int = FRAME_RGBA32F, out=None, w: int | None = None, h: int | None = None):
+        """Synchronous: voxels (d, rows, stride, 4) float32 into `out` (oh, stride >= ow, 4) of the format's dtype (a new
+        array if None). w, h: the slice size when rows or slices are padded."""
+        import numpy as np
+
+        assert voxels.dtype == np.float32 and voxels.ndim == 4 and voxels.shape[3] == 4 and voxels.flags["C_CONTIGUOUS"]
+        d = voxels.shape[0]
+        h = voxels.shape[1] if h is None else h
+        w = voxels.shape[2] if w is None else w
+        if out is None:
+            out = np.zeros((oh, ow, 4), FRAME_NUMPY[fmt])
+        assert out.dtype == np.dtype(FRAME_NUMPY[fmt]) and out.flags["C_CONTIGUOUS"] and out.shape[0] == oh
+        p = params if params is not None else retina_params()
+        err = _errbuf()
+        _check(self._lib.rt4_retina_project_host(
+            self._h, c_void_p(voxels.ctypes.data), voxels.shape[2], voxels.shape[1] * voxels.shape[2], w, h, d, byref(view),
+            byref(p), c_void_p(out.ctypes.data), fmt, out.shape[1], ow, oh, err, len(err)), err)
+        return out
+
     @property
     def kernel_shape(self) -> int:
         """Shape code of the trace kernel the scene runs on (rt4.h rt4_context_kernel_shape)."""
@@ -1659,3 +1805,86 @@ class Window:
         err = _errbuf()
         _check(self._lib.rt4_window_read_host(self._t, None, c_void_p(out.ctypes.data), err, len(err)), err)
         return out
+
+
+class Retina:
+    """rt4_retina: the 3D retina of a view as w x h x depth volumes. accumulate() folds frames into every slice's light
+    accumulator (and renders the G-buffer volume when the view is new); present() voxelizes when it must and projects a
+    RetinaView into a device frame, so another view of the same volume costs one projection. Close it before its Tracer.
+    After Tracer.set_scene call reset()."""
+
+    def __init__(self, tracer: Tracer, w: int, h: int, depth: int):
+        self._lib = tracer._lib
+        self._tracer = tracer  # keeps the context alive
+        self.w, self.h, self.depth = w, h, depth
+        t = c_void_p()
+        err = _errbuf()
+        _check(self._lib.rt4_retina_create(tracer._h, w, h, depth, byref(t), err, len(err)), err)
+        self._t = t
+
+    def close(self):
+        if getattr(self, "_t", None):
+            if getattr(self._tracer, "_h", None):  # a closed Tracer took the device buffers' context with it
+                self._lib.rt4_retina_destroy(self._t)
+            self._t = None
+
+    __del__ = close
+
+    def reset(self) -> None:
+        self._lib.rt4_retina_reset(self._t)
+
+    def accumulate(self, u: Uniforms, w_drct, depth_size: float, n_frames: int = 1, counter_ptr: int = 0,
+                   stream: int = 0) -> None:
+        """Asynchronous: n_frames more frames of the view u into every slice (rt4_retina_accumulate_device); another u,
+        w_drct or depth_size than the accumulated ones starts over."""
+        wd = (c_float * 4)(*w_drct)
+        err = _errbuf()
+        _check(self._lib.rt4_retina_accumulate_device(self._t, byref(u), wd, depth_size, n_frames, c_void_p(counter_ptr or None),
+                                                      c_void_p(stream or None), err, len(err)), err)
+
+    def present(self, view: RetinaView, k: float, frame_ptr: int, fmt: int, ow: int, oh: int, frame_stride: int | None = None,
+                params: RetinaParams | None = None, stream: int = 0) -> None:
+        """Asynchronous: the ow x oh picture of `view` into the device frame at frame_ptr (rt4_retina_present_device)."""
+        err = _errbuf()
+        _check(self._lib.rt4_retina_present_device(
+            self._t, byref(view), byref(params) if params is not None else None, k, c_void_p(frame_ptr or None), fmt,
+            ow if frame_stride is None else frame_stride, ow, oh, c_void_p(stream or None), err, len(err)), err)
+
+    def frames_done(self) -> int:
+        return int(self._lib.rt4_retina_frames_done(self._t))
+
+    # device pointers (row stride w, slice stride w * h)
+    def light_ptr(self) -> int:
+        return int(self._lib.rt4_retina_light(self._t) or 0)
+
+    def gbuffer_ptr(self) -> int:
+        return int(self._lib.rt4_retina_gbuffer(self._t) or 0)
+
+    def voxels_ptr(self) -> int:
+        return int(self._lib.rt4_retina_voxels(self._t) or 0)
+
+    def bytes(self) -> int:
+        return int(self._lib.rt4_retina_bytes(self._t))
+
+    def _read(self, which: int):
+        import numpy as np
+
+        shape = (self.depth, self.h, self.w)
+        out = np.zeros(shape + (4,), np.float32) if which == 2 else np.zeros(shape, (LIGHT_DTYPE, GBUFFER_DTYPE)[which])
+        ptrs = [None, None, None]
+        ptrs[which] = c_void_p(out.ctypes.data)
+        err = _errbuf()
+        _check(self._lib.rt4_retina_read_host(self._t, ptrs[0], ptrs[1], ptrs[2], err, len(err)), err)
+        return out
+
+    def light(self):
+        """Synchronous: the light volume on the host, (depth, h, w) of LIGHT_DTYPE."""
+        return self._read(0)
+
+    def gbuffer(self):
+        """Synchronous: the G-buffer volume, (depth, h, w) of GBUFFER_DTYPE."""
+        return self._read(1)
+
+    def voxels(self):
+        """Synchronous: the voxel volume of the last present, (depth, h, w, 4) float32."""
+        return self._read(2)

@@ -990,6 +990,154 @@ int rt4_light_info(const char* path, int32_t* w, int32_t* h, int64_t* frames_iss
 int rt4_light_load(const char* path, rt4_light_px* light, int32_t w, int32_t h, int64_t row_stride_px,
                    int64_t* frames_issued, uint32_t* seed, uint32_t* key, uint32_t* flags, char* err, size_t errlen);
 
+/* ---- 3D retina view: the w-slices as a volume, projected (no reference counterpart) ----
+ * An eye in 4D has a 3D retina: the matrix of rt4_uniforms (right_drct x top_drct) continued along the camera's fourth
+ * axis, rt4_orientation.w_drct. The reference shows three orthogonal 2D sections through its centre; here the retina is
+ * rendered whole, as `depth` slices, and projected to a picture that can be turned, so that the slices show parallax.
+ * Once a volume is accumulated, a new view of it costs one projection and no tracing.
+ * A volume of element type T holds voxel (s, i, j) at base + s*slice_stride + i*row_stride + j: j the column, i the row
+ * (row 0 on top), s the slice; strides in elements, row_stride >= w, slice_stride >= (h-1)*row_stride + w.
+ * Definition (fp32 round-to-nearest, no contraction, every fma explicit, division correctly rounded; comparisons with
+ * NaN are false and a NaN's payload is not defined; the kernels match it bit for bit).
+ *
+ * 1. Slices (host only). Slice `slice` of `depth` is an ordinary render whose matrix centre is shifted along w_drct:
+ *      t = (((float)slice + 0.5f) / (float)depth - 0.5f) * depth_size;
+ *      out = *u; when t != 0: out.vec_to_mtr[c] = fmaf(w_drct[c], t, u->vec_to_mtr[c]);
+ *      out.seed = (int32_t)((uint32_t)u->seed + (uint32_t)(slice - depth / 2) * 0x85EBCA6Bu)  (decorrelates the noise).
+ *    depth_size is the retina's extent along w_drct at the matrix, in scene units (the natural choice: u->mtr_sizes[1]).
+ *    The middle slice of an odd depth is *u byte for byte: the plain section.
+ *
+ * 2. Voxelize. L a light volume, G the G-buffer volume of the same slices (both w x h x d), k the tone-map constant.
+ *      c_ch = (L.n == 0) ? 0 : 1.0f - 1.0f / fmaf(k, L.mean_ch, 1.0f)      (the resolve's formula);
+ *      edge(v) iff G(v).surface >= 0 and one of v's six face neighbours that lie inside the volume has another surface
+ *      value (-1, the sky, included);
+ *      a = edge ? alpha_edge : (G(v).surface >= 0 ? alpha_fill : alpha_sky);
+ *      V(v) = (a*c_r, a*c_g, a*c_b, a)                                        (plain multiplies: premultiplied).
+ *    Why edges: in a 4D scene nearly every voxel hits something (the ground fills half the retina), and a volume of
+ *    one opacity shows only its own faces. The sheets where the surface number changes are the objects' outlines.
+ *
+ * 3. Project. A view gives the picture's rays in voxel coordinates (x column, y row, z slice, voxel centres at the
+ *    integers). For pixel (i, j) of the ow x oh picture (row 0 on top), c over x, y, z:
+ *      a = ((float)j + 0.5f) / (float)ow - 0.5f;  b = 0.5f - ((float)i + 0.5f) / (float)oh;
+ *      base_c = fmaf(b, dv_c, fmaf(a, du_c, origin_c));  sample n: f_c = fmaf((float)n + 0.5f, dt_c, base_c).
+ *    A sample is outside unless f_c > -1.0f && f_c < (float)N_c on all three axes (N = w, h, d; tested before any
+ *    conversion to an integer; NaN is outside). An outside sample contributes nothing. Otherwise x0 = floorf(f_x),
+ *    wx1 = f_x - x0, wx0 = 1.0f - wx1, y and z alike; the eight taps run tz outer, ty, tx inner, tap (tx, ty, tz) is
+ *    voxel (x0+tx, y0+ty, z0+tz) with weight (wz * wy) * wx; a tap whose index lies outside [0, N_c) on any axis is
+ *    skipped; S_c = fmaf(weight, V_c, S_c) from 0, for r, g, b, a.
+ *    Composite, from C = 0, T = 1, for n = 0 .. steps-1, inside samples only:
+ *      C_c = fmaf(T, S_c, C_c);  T = T * fmaxf(1.0f - S_a, 0.0f);  then the ray stops if T < t_min.
+ *    (fmaxf as IEEE maxNum: a NaN S_a gives 0.) The pixel is fmaf(T, background_c, C_c), alpha 1, stored through the
+ *    format's rule (half: round to nearest even; RGBA8: the rule of rt4_frame_format).
+ *    The kernel skips the samples ahead of and behind the volume in one step per ray; the bytes are those of the loop
+ *    above (rt4_retina.h has the argument). */
+#define RT4_RETINA_MAX_DEPTH 256
+#define RT4_RETINA_MAX_STEPS 4096
+/* RT4_ERR_ARG for a NULL pointer, depth outside 1..RT4_RETINA_MAX_DEPTH, slice outside [0, depth), or a depth_size that
+ * is not finite and > 0. Host only. */
+int rt4_retina_slice_uniforms(const rt4_uniforms* u, const float w_drct[4], int32_t depth, float depth_size,
+                              int32_t slice, rt4_uniforms* out);
+
+typedef struct rt4_retina_params {
+  float alpha_sky, alpha_fill, alpha_edge; /* opacity of a voxel that misses / hits / hits next to another surface: [0, 1] */
+  float t_min;                             /* a ray stops once its transmittance falls below this: [0, 1) */
+  float background[3];                     /* what shows through, times the ray's last transmittance */
+} rt4_retina_params;
+/* 0, 1/32, 0.5, 1/256, black. Starting points, looked at on turntables of sphere, tiger and hypercube. */
+void rt4_retina_params_default(rt4_retina_params* p);
+
+typedef struct rt4_retina_view { /* the picture's rays in voxel coordinates: x column, y row, z slice, centres at integers */
+  float origin[3], du[3], dv[3], dt[3];
+  int32_t steps; /* samples per ray, 1..RT4_RETINA_MAX_STEPS */
+} rt4_retina_view;
+/* An orthographic view of the retina box (host only). The box is size[0] x size[1] x size[2] scene units (mtr_sizes[0],
+ * mtr_sizes[1], depth_size) around the origin, X right, Y up, Z along the slices; scene to voxel per axis:
+ * (X/Sx + 0.5)*w - 0.5, (0.5 - Y/Sy)*h - 0.5, (Z/Sz + 0.5)*d - 0.5. With yaw = pitch = 0 the rays run along +Z, slice 0
+ * first. yaw turns about the retina's up axis: forward F = (sin yaw, 0, cos yaw), right R = (cos yaw, 0, -sin yaw);
+ * then pitch about R: F' = cos(pitch) F - sin(pitch) Y (a positive pitch looks down on the box), U = cos(pitch) Y +
+ * sin(pitch) F. The picture spans extent x extent*oh/ow scene units around the box centre (extent 0: the box diagonal):
+ * du = R * extent, dv = U * extent*oh/ow. Every ray starts on the plane, normal to F', that touches the box in front
+ * (e = (|F'x| Sx + |F'y| Sy + |F'z| Sz) / 2 before the centre's plane: at most half a diagonal) and runs 2e, to the
+ * plane that touches it behind; the step is step_voxels times the smallest voxel edge min(Sx/w, Sy/h, Sz/d) and
+ * steps = ceil(2e / step - 1/1024), at least 1 (an angle that is a right angle but for its float rounding adds no step).
+ * Computed in double; each of the 12 floats is rounded once. RT4_ERR_ARG for a NULL pointer,
+ * w, h, d, ow or oh < 1, a size, extent, angle or step_voxels that is not finite, a size or step_voxels <= 0, an
+ * extent < 0, or more than RT4_RETINA_MAX_STEPS steps. */
+int rt4_retina_view_make(int32_t w, int32_t h, int32_t d, const float size[3], float yaw, float pitch, float extent,
+                         int32_t ow, int32_t oh, float step_voxels, rt4_retina_view* view, char* err, size_t errlen);
+
+/* Step 2: d_voxels (float4 per voxel, 16-byte aligned) from d_light and d_gbuf, each with its own row and slice stride.
+ * RT4_ERR_ARG, nothing written, for a NULL pointer, w or h outside [1, 65535], d outside 1..RT4_RETINA_MAX_DEPTH, a
+ * stride too small, a pointer not aligned to 16 B, an alpha outside [0, 1], a t_min outside [0, 1) (a NaN fails both),
+ * or a voxel volume that overlaps an input. Asynchronous on `stream`, no allocation. Ordered with the context's other
+ * launches. */
+int rt4_retina_voxelize_device(rt4_context* ctx, const rt4_light_px* d_light, int64_t light_row_stride,
+                               int64_t light_slice_stride, const rt4_gbuffer_px* d_gbuf, int64_t gbuf_row_stride,
+                               int64_t gbuf_slice_stride, float k, const rt4_retina_params* params, float* d_voxels,
+                               int64_t vox_row_stride, int64_t vox_slice_stride, int32_t w, int32_t h, int32_t d,
+                               void* stream, char* err, size_t errlen);
+/* The same on host volumes (synchronous; the padding of the voxel volume keeps its bytes). */
+int rt4_retina_voxelize_host(rt4_context* ctx, const rt4_light_px* light, int64_t light_row_stride,
+                             int64_t light_slice_stride, const rt4_gbuffer_px* gbuf, int64_t gbuf_row_stride,
+                             int64_t gbuf_slice_stride, float k, const rt4_retina_params* params, float* voxels,
+                             int64_t vox_row_stride, int64_t vox_slice_stride, int32_t w, int32_t h, int32_t d, char* err,
+                             size_t errlen);
+/* Step 3: the ow x oh picture of `view` in `format` from a voxel volume; of params only t_min and background are used,
+ * all are checked. Any finite view is accepted (rt4_retina_view_make need not have made it), and a view with NaN or
+ * infinite numbers gives defined pixels too (the background wherever no sample is inside). RT4_ERR_ARG, nothing
+ * written, for a NULL pointer, an unknown format, w or h outside [1, 65535], d outside 1..RT4_RETINA_MAX_DEPTH, ow or
+ * oh outside [1, 65535], steps outside 1..RT4_RETINA_MAX_STEPS, a stride too small, a misaligned pointer (volume 16 B,
+ * frame its pixel size), params as in voxelize, or a frame that overlaps the volume. Every load is index-checked,
+ * offsets are 64-bit and the loop is bounded by steps. Asynchronous on `stream`, no allocation. Ordered with the
+ * context's other launches. */
+int rt4_retina_project_device(rt4_context* ctx, const float* d_voxels, int64_t vox_row_stride, int64_t vox_slice_stride,
+                              int32_t w, int32_t h, int32_t d, const rt4_retina_view* view,
+                              const rt4_retina_params* params, void* d_frame, int32_t format, int64_t frame_stride,
+                              int32_t ow, int32_t oh, void* stream, char* err, size_t errlen);
+/* The same on host buffers (synchronous; frame bytes outside [0,ow) x [0,oh) keep their values). */
+int rt4_retina_project_host(rt4_context* ctx, const float* voxels, int64_t vox_row_stride, int64_t vox_slice_stride,
+                            int32_t w, int32_t h, int32_t d, const rt4_retina_view* view, const rt4_retina_params* params,
+                            void* frame, int32_t format, int64_t frame_stride, int32_t ow, int32_t oh, char* err,
+                            size_t errlen);
+
+/* The volume with its state: a light volume, a G-buffer volume and a voxel volume of w x h x depth (no padding: row
+ * stride w, slice stride w*h), allocated at creation (rt4_retina_bytes), and what they were accumulated and voxelized
+ * for. w, h in [1, 8191] (the light render's limit), depth 1..RT4_RETINA_MAX_DEPTH. A failed allocation returns
+ * RT4_ERR_HIP with *out = NULL, which every call below accepts. Destroy it before its context. After
+ * rt4_context_set_scene call rt4_retina_reset. */
+typedef struct rt4_retina rt4_retina;
+int rt4_retina_create(rt4_context* ctx, int32_t w, int32_t h, int32_t depth, rt4_retina** out, char* err, size_t errlen);
+void rt4_retina_destroy(rt4_retina* ret); /* waits for the context's launches in flight */
+/* The next accumulate starts over (frames_done 0), as the first after creation does. */
+void rt4_retina_reset(rt4_retina* ret);
+/* After create or reset, or when the bytes of u, w_drct or depth_size differ from the accumulated ones (then it resets
+ * first): empties the light volume and renders the G-buffer volume, one rt4_render_gbuffer_device per slice. Then, for
+ * every slice, folds frames frames_done + 1 .. frames_done + n_frames of rt4_progressive_uniforms of the slice's
+ * uniforms (rt4_retina_slice_uniforms) into that slice's accumulator with rt4_render_light_device: every slice holds
+ * exactly the bytes of those calls. u->resolution must be (w, h); n_frames >= 1; d_counter counts as usual.
+ * One launch per slice and chunk of frames: a slice of a window-sized retina does not fill the GPU.
+ * Asynchronous as rt4_render_light_device is. An error leaves the object reset. */
+int rt4_retina_accumulate_device(rt4_retina* ret, const rt4_uniforms* u, const float w_drct[4], float depth_size,
+                                 int32_t n_frames, unsigned long long* d_counter, void* stream, char* err, size_t errlen);
+/* Voxelizes only when the volume was accumulated further, or the alphas or k differ, since the last voxelize; then
+ * projects `view` into d_frame (ow x oh, `format`, stride in pixels). params NULL = the defaults. RT4_ERR_ARG before
+ * the first accumulate. Asynchronous on `stream`: no allocation, no synchronisation. */
+int rt4_retina_present_device(rt4_retina* ret, const rt4_retina_view* view, const rt4_retina_params* params, float k,
+                              void* d_frame, int32_t format, int64_t frame_stride, int32_t ow, int32_t oh, void* stream,
+                              char* err, size_t errlen);
+/* Frames folded into every slice since the last reset. */
+int64_t rt4_retina_frames_done(const rt4_retina* ret);
+/* Device pointers of the three volumes. */
+rt4_light_px* rt4_retina_light(const rt4_retina* ret);
+rt4_gbuffer_px* rt4_retina_gbuffer(const rt4_retina* ret);
+float* rt4_retina_voxels(const rt4_retina* ret);
+/* The three copied to host volumes of w x h x depth elements (any may be NULL). Synchronous: waits for the context's
+ * launches. */
+int rt4_retina_read_host(rt4_retina* ret, rt4_light_px* light, rt4_gbuffer_px* gbuf, float* voxels, char* err,
+                         size_t errlen);
+/* Device bytes the object owns. */
+uint64_t rt4_retina_bytes(const rt4_retina* ret);
+
 /* ---- diagnostics (used by the parity tests; not on the render path) ------------------------- */
 /* Bytes of the context's frame-colour scratch for pipelined frames (0 before any pipelined launch or
  * reservation; a scene that runs frame by frame never allocates it). */
