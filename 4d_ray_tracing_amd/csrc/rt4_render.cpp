@@ -71,6 +71,14 @@
 //                   empty selection, is a whole-frame pass; the loop never stops early. One line per pass, the min /
 //                   median / max of n at the end, and <prefix>_<section>_n.<ext>: n over the largest n as grey.
 //                   Defaults 8, 4, 4, 4, 1: the values of the study in DESIGN.md §4.39)
+//                   [--supersample S]  (needs --light, S 1..8: anti-aliased pixels, DESIGN.md §4.48. -W/-H, or the
+//                   properties' cells, name the output; the accumulation (the -n frames, --adaptive, --light-resume)
+//                   runs at S times that, the view of rt4_upscale_uniforms, whose pixel centres are an S x S grid
+//                   inside every output pixel, and one rt4_light_downsample_device per section follows. The resolve, the
+//                   statistics, --noise-map, --light-denoise, --denoise, --window, the images and the _n picture see the
+//                   output-resolution accumulator; --light-checkpoint saves the fine one, which --light-resume with the same S
+//                   continues. -n keeps meaning frames at the render resolution: S^2 times fewer frames cast the same
+//                   rays. Not with --light-gpus, --light-pool or --retina; S times the output at most 8191 per side)
 //                   [--retina D [--retina-size X] [--retina-view YAW PITCH] [--retina-turntable N] [--retina-step S]]
 //                   (the 3D retina view, DESIGN.md §4.47: the -n frames go into a D-slice light volume of the section's
 //                   view, the slices spread over X scene units along the camera's w axis (default: the matrix height),
@@ -482,6 +490,8 @@ struct Options {
   int denoise_levels = 0, light_denoise_levels = -1, window_scale = 0;
   bool window_nearest = false, light = false, noise_map = false;
   float noise_threshold = 1.0f / 255.0f;  // --noise-threshold: one 8-bit step
+  int supersample = 0;                    // --supersample S: 0 = off
+  bool supersample_given = false;
   // --adaptive (needs --light): the loop of DESIGN.md §4.39 in place of -n uniform frames; -n is then the budget in
   // whole-frame equivalents. The defaults are the values of that section's study.
   bool adaptive = false, ad_given = false;
@@ -539,6 +549,7 @@ Options parse_args(int argc, char** argv) {
     else if (a == "--light") o.light = true;
     else if (a == "--noise-map") o.noise_map = true;
     else if (a == "--noise-threshold") o.noise_threshold = static_cast<float>(std::atof(next()));
+    else if (a == "--supersample") o.supersample = std::atoi(next()), o.supersample_given = true;
     else if (a == "--light-resume") o.light_resume_path = next();
     else if (a == "--light-checkpoint") o.light_checkpoint_path = next();
     else if (a == "--light-gpus") o.light_gpus = std::atoi(next());
@@ -575,6 +586,7 @@ Options parse_args(int argc, char** argv) {
         die("--light-denoise", "levels must be 0..6");
     } else die("unknown argument", a.c_str());
   }
+  if (o.supersample_given && (o.supersample < 1 || o.supersample > RT4_SUPERSAMPLE_MAX)) die("--supersample", "S must be 1..8");
   o.format = o.fmt_name == "f16" ? RT4_FRAME_RGBA16F : o.fmt_name == "rgba8" ? RT4_FRAME_RGBA8 : RT4_FRAME_RGBA32F;
   if (o.pool()) o.frames = 0;  // nothing is rendered
   return o;
@@ -602,6 +614,15 @@ void refuse_retina_conflicts(const Options& o) {
                          !std::isfinite(o.retina_pitch) || o.retina_turntable < 0 || !(o.retina_step > 0.0f) ||
                          !std::isfinite(o.retina_step)))
     die(f, "size >= 0 (0: the matrix height), a view of two angles in degrees, turntable >= 0, step > 0");
+}
+
+// --supersample: the render is S times the output, and rt4_render_light_device takes at most 8191 per side. With -W -H
+// refuse_conflicts knows the output; the properties' cells are known once load_inputs has read them.
+void refuse_supersample_size(const Options& o, int32_t w, int32_t h) {
+  const long long fw = static_cast<long long>(w) * o.supersample, fh = static_cast<long long>(h) * o.supersample;
+  if (fw > 8191 || fh > 8191)
+    die("--supersample", ("the render would be " + std::to_string(fw) + "x" + std::to_string(fh) +
+                          ": the light render takes at most 8191 x 8191").c_str());
 }
 
 // Every combination of flags that is refused whatever the files hold, in one place: the first check that fails is the
@@ -661,6 +682,10 @@ void refuse_conflicts(const Options& o) {
   // pixel bands over GPUs 0..gpus-1, one RCCL gather (one section, resting camera)
   if (o.gpus > 0 && (o.three || o.moving())) die("--gpus", "needs one section and a resting camera");
   if (o.gpus > 0 && (o.frames < 1 || o.band < 1)) die("--gpus", "frames and band must be >= 1");
+  if (o.supersample_given && !o.light) die("--supersample", "needs --light: it averages light accumulators");
+  if (o.supersample_given && (o.light_gpus != 0 || o.pool() || o.retina))
+    die("--supersample", "not with --light-gpus, --light-pool or --retina");
+  if (o.supersample_given && o.width > 0 && o.height > 0) refuse_supersample_size(o, o.width, o.height);
 }
 
 // --gpus / --light-gpus without --rehearse (a rehearsal puts every rank on device 0 and reports a missing device per rank)
@@ -676,6 +701,11 @@ struct Section {
   const char *name, *window;  // "yxz", and whose cells and cell_size in the properties: "main" / "additional"
   int32_t w = 0, h = 0;
   rt4_uniforms base = {};           // from the properties, at w x h
+  // What the frames are rendered at: w x h and base, or with --supersample S the view at S times the resolution
+  // (rt4_upscale_uniforms), whose accumulator d_fine is downsampled into d_light.
+  int32_t fw = 0, fh = 0;
+  rt4_uniforms fine = {};
+  rt4_light_px* d_fine = nullptr;
   int32_t win_scale = 0;            // --window: this section's scale
   void* d_frame = nullptr;          // the image, in the run's frame format
   rt4_light_px* d_light = nullptr;  // --light: the accumulator
@@ -685,6 +715,9 @@ struct Section {
   size_t pixels() const { return static_cast<size_t>(w) * h; }
   size_t frame_bytes(int32_t px) const { return pixels() * static_cast<size_t>(px); }
   rt4_region region() const { return rt4_region{0, 0, w, h, 0, 0}; }
+  size_t fine_pixels() const { return static_cast<size_t>(fw) * fh; }
+  rt4_region fine_region() const { return rt4_region{0, 0, fw, fh, 0, 0}; }
+  rt4_light_px* accum() const { return d_fine ? d_fine : d_light; }  // --light: the accumulator the frames fold into
   float tone() const { return base.light_to_color_conversion_coefficient; }  // of the tone curve (resolve, filter, noise)
 };
 
@@ -739,14 +772,14 @@ void load_light_resumed(const Options& o, Run& r) {
   int32_t ck_w = 0, ck_h = 0;
   RT4_CHECK(rt4_light_info(path, &ck_w, &ck_h, nullptr, &ck_seed, &ck_key, &ck_flags, err, sizeof err));
   if (ck_flags & RT4_LIGHT_POOLED) die("--light-resume", "the checkpoint pools runs of several seeds: it cannot be resumed");
-  if (ck_w != s.w || ck_h != s.h)
+  if (ck_w != s.fw || ck_h != s.fh)
     die("--light-resume", ("the checkpoint holds a " + std::to_string(ck_w) + "x" + std::to_string(ck_h) + " accumulator, not " +
-                           std::to_string(s.w) + "x" + std::to_string(s.h)).c_str());
+                           std::to_string(s.fw) + "x" + std::to_string(s.fh)).c_str());
   if (ck_seed != o.seed) die("--light-resume", "the checkpoint was made with another --seed");
   if (ck_key != 0u && ck_key != r.run_key)
     die("--light-resume", "the checkpoint was made with another scene, properties or camera");
-  r.light_start.resize(s.pixels());
-  RT4_CHECK(rt4_light_load(path, r.light_start.data(), s.w, s.h, s.w, &r.frames_done, nullptr, nullptr, nullptr, err,
+  r.light_start.resize(s.fine_pixels());
+  RT4_CHECK(rt4_light_load(path, r.light_start.data(), s.fw, s.fh, s.fw, &r.frames_done, nullptr, nullptr, nullptr, err,
                            sizeof err));
   if (r.frames_done + o.frames > 0xFFFFFFFFll) die("--light-resume", "frame numbers beyond 2^32 - 1");
   r.cam.frame_number = static_cast<uint32_t>(r.frames_done + 1);
@@ -764,7 +797,7 @@ void load_pool(const Options& o, Run& r) {
     uint32_t ck_seed = 0, ck_key = 0;
     RT4_CHECK(rt4_light_info(path, &fw, &fh, &issued, &ck_seed, &ck_key, nullptr, err, sizeof err));
     if (f == 0) {
-      s.w = fw, s.h = fh, r.pool_seed = ck_seed, r.pool_key = ck_key, r.pool_issued = issued;
+      s.w = s.fw = fw, s.h = s.fh = fh, r.pool_seed = ck_seed, r.pool_key = ck_key, r.pool_issued = issued;
       r.light_start.resize(o.light_pool.size() * s.pixels());
     }
     if (fw != s.w || fh != s.h) die("--light-pool: another image size than the first file's", path);
@@ -803,12 +836,18 @@ Run load_inputs(const Options& o) {
   for (Section& s : r.sections)
     if (!(sized && &s == &yxz)) RT4_CHECK(rt4_window_cells(r.props, s.window, &s.w, &s.h, err, sizeof err));
   if (sized) yxz.w = o.width, yxz.h = o.height;
-  for (Section& s : r.sections)
+  for (Section& s : r.sections) {
     RT4_CHECK(rt4_uniforms_from_properties(r.props, s.w, s.h, s.id, &s.base, nullptr, err, sizeof err));
+    s.fw = s.w, s.fh = s.h, s.fine = s.base;
+    if (!o.supersample_given) continue;
+    refuse_supersample_size(o, s.w, s.h);
+    s.fw = s.w * o.supersample, s.fh = s.h * o.supersample;
+    if (rt4_upscale_uniforms(&s.base, o.supersample, &s.fine) != RT4_OK) die("--supersample", "rt4_upscale_uniforms refused the view");
+  }
   RT4_CHECK(rt4_camera_init(r.props, &r.cam, err, sizeof err));
   rt4_camera c0 = r.cam;
   rt4_uniforms u0;
-  RT4_CHECK(rt4_camera_frame_uniforms(&c0, &yxz.base, yxz.id, 0, &u0));
+  RT4_CHECK(rt4_camera_frame_uniforms(&c0, &yxz.fine, yxz.id, 0, &u0));
   r.run_key = rt4_accum_key(r.scene, &u0);
 
   if (!o.resume_path.empty()) load_resumed(o, r);
@@ -830,11 +869,12 @@ void window_scales(const Options& o, Run& r) {
 // main.cpp's seed ^= generateSeed(timer), deterministic.
 int32_t frame_seed(uint32_t seed, int64_t n) { return static_cast<int32_t>(seed ^ (static_cast<uint32_t>(n) * 0x9E3779B9u)); }
 
-// The uniforms of the run's -n frames of a section with a resting camera; the camera's frame number moves on by -n.
+// The uniforms of the run's -n frames of a section with a resting camera, at the resolution they are rendered at
+// (s.fine: s.base unless --supersample); the camera's frame number moves on by -n.
 std::vector<rt4_uniforms> resting_frames(const Options& o, Run& r, const Section& s) {
   std::vector<rt4_uniforms> us(static_cast<size_t>(std::max(o.frames, 0)));
   for (int64_t n = 1; n <= o.frames; n++)
-    RT4_CHECK(rt4_camera_frame_uniforms(&r.cam, &s.base, s.id, frame_seed(o.seed, r.frames_done + n), &us[n - 1]));
+    RT4_CHECK(rt4_camera_frame_uniforms(&r.cam, &s.fine, s.id, frame_seed(o.seed, r.frames_done + n), &us[n - 1]));
   return us;
 }
 
@@ -919,11 +959,17 @@ void pipelined_frames(const Options& o, Run& r) {
 // --light: one empty accumulator per section; the main one continues --light-resume's, or is --light-pool's files
 // merged in order, RT4_LIGHT_MERGE_MAX of them per call, and resolved into the section's frame.
 void open_light(const Options& o, Run& r) {
-  for (Section& s : r.sections) s.d_light = device_alloc<rt4_light_px>(s.pixels(), true);
+  for (Section& s : r.sections) {
+    s.d_light = device_alloc<rt4_light_px>(s.pixels(), true);
+    if (o.supersample_given) s.d_fine = device_alloc<rt4_light_px>(s.fine_pixels(), true);  // --supersample: the frames' own
+  }
   Section& s = r.sections[0];
   const size_t bytes = s.pixels() * sizeof(rt4_light_px);
   r.light_issued = o.pool() ? r.pool_issued : r.frames_done + o.frames;
-  if (!o.light_resume_path.empty()) HIP_CHECK(hipMemcpy(s.d_light, r.light_start.data(), bytes, hipMemcpyHostToDevice));
+  if (!o.light_resume_path.empty())
+    HIP_CHECK(hipMemcpy(s.accum(), r.light_start.data(), s.fine_pixels() * sizeof(rt4_light_px), hipMemcpyHostToDevice));
+  if (!o.light_resume_path.empty() && s.d_fine)  // with -n 0 nothing else brings the resumed strata into d_light
+    RT4_CHECK(rt4_light_downsample_device(r.ctx, s.d_fine, s.fw, s.d_light, s.w, s.w, s.h, o.supersample, nullptr, err, sizeof err));
   if (!o.pool()) return;
   std::vector<rt4_light_px> merged(s.pixels());  // empty: value-initialised
   const int64_t plane = static_cast<int64_t>(s.pixels());
@@ -941,8 +987,9 @@ void open_light(const Options& o, Run& r) {
 // frame; frame g is rt4_progressive_uniforms(ub: the section's uniforms with --seed, g), g running on across the
 // passes. Returns the loop's last frame number, whatever share of the image each frame covered.
 uint32_t adaptive_passes(const Options& o, Run& r, const Section& s, const rt4_uniforms& ub) {
-  const rt4_region reg = s.region();
-  const long long tiles = static_cast<long long>((s.w + 7) / 8) * ((s.h + 7) / 8);
+  const rt4_region reg = s.fine_region();  // the render resolution, as the accumulator the frames fold into
+  rt4_light_px* const d_acc = s.accum();
+  const long long tiles = static_cast<long long>((s.fw + 7) / 8) * ((s.fh + 7) / 8);
   const long long budget = static_cast<long long>(o.frames) * tiles;
   uint32_t* d_tiles = device_alloc<uint32_t>(static_cast<size_t>(tiles));
   uint32_t* d_n = device_alloc<uint32_t>(1);
@@ -959,7 +1006,7 @@ uint32_t adaptive_passes(const Options& o, Run& r, const Section& s, const rt4_u
   sel.min_frames = warm;
   if (warm > 0) {
     pass_uniforms(warm);
-    RT4_CHECK(rt4_render_light_device(r.ctx, pus.data(), warm, &reg, s.d_light, s.w, r.d_count, nullptr, err, sizeof err));
+    RT4_CHECK(rt4_render_light_device(r.ctx, pus.data(), warm, &reg, d_acc, s.fw, r.d_count, nullptr, err, sizeof err));
     spent += warm * tiles;
     std::printf("adaptive %s: warmup tiles %lld frames %d\n", s.name, tiles, warm);
   }
@@ -967,7 +1014,7 @@ uint32_t adaptive_passes(const Options& o, Run& r, const Section& s, const rt4_u
     const char* kind = "full";
     long long listed = tiles;
     if (!(o.ad_full_every > 0 && n_pass % o.ad_full_every == 0)) {
-      RT4_CHECK(rt4_light_select_tiles_device(r.ctx, s.d_light, s.w, s.w, s.h, ub.light_to_color_conversion_coefficient, &sel,
+      RT4_CHECK(rt4_light_select_tiles_device(r.ctx, d_acc, s.fw, s.fw, s.fh, ub.light_to_color_conversion_coefficient, &sel,
                                               d_tiles, d_n, nullptr, nullptr, err, sizeof err));
       uint32_t n_sel = 0;  // the one 4-byte read of the pass (synchronises)
       HIP_CHECK(hipMemcpy(&n_sel, d_n, sizeof n_sel, hipMemcpyDeviceToHost));
@@ -978,9 +1025,9 @@ uint32_t adaptive_passes(const Options& o, Run& r, const Section& s, const rt4_u
     if (n <= 0) break;
     pass_uniforms(n);
     if (listed == tiles && kind[0] != 't')  // a selection that lists every tile still goes through the tile path
-      RT4_CHECK(rt4_render_light_device(r.ctx, pus.data(), n, &reg, s.d_light, s.w, r.d_count, nullptr, err, sizeof err));
+      RT4_CHECK(rt4_render_light_device(r.ctx, pus.data(), n, &reg, d_acc, s.fw, r.d_count, nullptr, err, sizeof err));
     else
-      RT4_CHECK(rt4_render_light_tiles_device(r.ctx, pus.data(), n, &reg, d_tiles, static_cast<int32_t>(listed), s.d_light, s.w,
+      RT4_CHECK(rt4_render_light_tiles_device(r.ctx, pus.data(), n, &reg, d_tiles, static_cast<int32_t>(listed), d_acc, s.fw,
                                               r.d_count, nullptr, err, sizeof err));
     spent += n * listed;
     std::printf("adaptive %s: %s tiles %lld frames %d\n", s.name, kind, listed, n);
@@ -992,13 +1039,15 @@ uint32_t adaptive_passes(const Options& o, Run& r, const Section& s, const rt4_u
 }
 
 // --light, one section: its frames into its accumulator (frame n of every section has the same seed, as in
-// render_colour_frames) in one of three ways, then the image: the accumulator resolved into the section's frame.
+// render_colour_frames) in one of three ways, with --supersample at S times the resolution and downsampled once, then
+// the image: the accumulator resolved into the section's frame.
 // frame_number: the camera's before the first section, so that every section renders the same frames.
 void render_light_section(const Options& o, const ShardHooks& hooks, Run& r, Section& s, uint32_t frame_number) {
   r.cam.frame_number = frame_number;
   const std::vector<rt4_uniforms> lus = resting_frames(o, r, s);
-  s.last_u = lus.back();
-  const rt4_region reg = s.region();
+  s.last_u = lus.back();  // the pose the output-resolution images show: the G-buffer and the window render it at w x h
+  s.last_u.resolution[0] = s.base.resolution[0], s.last_u.resolution[1] = s.base.resolution[1];
+  const rt4_region reg = s.fine_region();
   if (o.light_gpus > 0) {
     // the accumulator of the section from light_gpus devices; resolve and everything after it run here, on the root's
     // accumulator, as in a one-GPU run
@@ -1009,12 +1058,14 @@ void render_light_section(const Options& o, const ShardHooks& hooks, Run& r, Sec
   } else if (o.adaptive) {
     rt4_uniforms ub;
     r.cam.frame_number = frame_number;
-    RT4_CHECK(rt4_camera_frame_uniforms(&r.cam, &s.base, s.id, static_cast<int32_t>(o.seed), &ub));
+    RT4_CHECK(rt4_camera_frame_uniforms(&r.cam, &s.fine, s.id, static_cast<int32_t>(o.seed), &ub));
     r.cam.frame_number = frame_number + static_cast<uint32_t>(o.frames);  // as the uniform frames above left it
     r.light_issued = adaptive_passes(o, r, s, ub);
   } else {
-    RT4_CHECK(rt4_render_light_device(r.ctx, lus.data(), o.frames, &reg, s.d_light, s.w, r.d_count, nullptr, err, sizeof err));
+    RT4_CHECK(rt4_render_light_device(r.ctx, lus.data(), o.frames, &reg, s.accum(), s.fw, r.d_count, nullptr, err, sizeof err));
   }
+  if (s.d_fine)  // the S x S strata of every output pixel into its accumulator; everything below reads that one
+    RT4_CHECK(rt4_light_downsample_device(r.ctx, s.d_fine, s.fw, s.d_light, s.w, s.w, s.h, o.supersample, nullptr, err, sizeof err));
   RT4_CHECK(rt4_light_resolve_device(r.ctx, s.d_light, s.w, s.tone(), s.d_frame, o.format, s.w, s.w, s.h, nullptr, err,
                                      sizeof err));
 }
@@ -1125,7 +1176,9 @@ void light_outputs(const Options& o, Run& r, const Section& s) {
   if (o.raw || checkpoint || o.adaptive) acc = device_read<rt4_light_px>(s.d_light, npx);
   if (o.raw) write_raw(o.out + "_" + s.name + "_light.raw", acc.data(), npx * sizeof(rt4_light_px));
   if (checkpoint) {
-    RT4_CHECK(rt4_light_save(o.light_checkpoint_path.c_str(), acc.data(), s.w, s.h, s.w, r.light_issued,
+    // with --supersample the fine accumulator, so that a resume continues the bytes the frames fold into
+    const std::vector<rt4_light_px> fine = s.d_fine ? device_read<rt4_light_px>(s.d_fine, s.fine_pixels()) : std::vector<rt4_light_px>();
+    RT4_CHECK(rt4_light_save(o.light_checkpoint_path.c_str(), s.d_fine ? fine.data() : acc.data(), s.fw, s.fh, s.fw, r.light_issued,
                              o.pool() ? r.pool_seed : o.seed, o.pool() ? r.pool_key : r.run_key, o.pool() ? RT4_LIGHT_POOLED : 0u,
                              err, sizeof err));
     std::printf("light checkpoint %s (frames issued %lld%s)\n", o.light_checkpoint_path.c_str(),
@@ -1243,6 +1296,7 @@ void close_render(const Options& o, Run& r) {
   for (Section& s : r.sections) {
     rt4_temporal_destroy(s.temporal);
     if (s.d_light) (void)hipFree(s.d_light);
+    if (s.d_fine) (void)hipFree(s.d_fine);
     (void)hipFree(s.d_frame);
   }
   (void)hipFree(r.d_count);

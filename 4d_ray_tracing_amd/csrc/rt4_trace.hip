@@ -3070,6 +3070,7 @@ int rt4_debug_sqrt_thresholds(float r, float* gt, float* lt) {
 #include "rt4_light_denoise.h"
 #include "rt4_light_tiles.h"
 #include "rt4_light_merge.h"
+#include "rt4_light_downsample.h"
 #include "rt4_retina.h"
 
 extern "C" {

@@ -190,6 +190,7 @@ class TileSelectParams(Structure):  # rt4.h rt4_tile_select_params
 
 SELECT_MAX_DILATE = 2  # rt4.h RT4_SELECT_MAX_DILATE
 LIGHT_MERGE_MAX = 16  # rt4.h RT4_LIGHT_MERGE_MAX
+SUPERSAMPLE_MAX = 8  # rt4.h RT4_SUPERSAMPLE_MAX
 LIGHT_POOLED = 0x1  # rt4.h RT4_LIGHT_POOLED: a light checkpoint of several seeds, not resumable
 
 
@@ -380,6 +381,9 @@ def _load(path=None):
                                     c_void_p] + E, c_int),
         "rt4_light_merge_host": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32] + E,
                                  c_int),
+        "rt4_light_downsample_device": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                         c_void_p] + E, c_int),
+        "rt4_light_downsample_host": ([c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32] + E, c_int),
         "rt4_light_bands_unpermute_device": ([c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p] + E,
                                              c_int),
         "rt4_frame_split": ([c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)] + E, c_int),
@@ -459,7 +463,7 @@ EXPORTED = (
     "rt4_tile_select_params_default rt4_light_select_tiles_device rt4_light_select_tiles_host "
     "rt4_render_light_tiles_device rt4_render_light_tiles_host rt4_context_select_bytes "
     "rt4_light_merge_device rt4_light_merge_host rt4_light_bands_unpermute_device rt4_frame_split "
-    "rt4_light_save rt4_light_info rt4_light_load "
+    "rt4_light_save rt4_light_info rt4_light_load rt4_light_downsample_device rt4_light_downsample_host "
     "rt4_retina_slice_uniforms rt4_retina_params_default rt4_retina_view_make rt4_retina_voxelize_device "
     "rt4_retina_voxelize_host rt4_retina_project_device rt4_retina_project_host rt4_retina_create rt4_retina_destroy "
     "rt4_retina_reset rt4_retina_accumulate_device rt4_retina_present_device rt4_retina_frames_done rt4_retina_light "
@@ -1350,6 +1354,34 @@ class Tracer:
                                               srcs.shape[2], srcs.shape[1] * srcs.shape[2], srcs.shape[0], w, h, err,
                                               len(err)), err)
         return dst
+
+    def light_downsample_device(self, fine_ptr: int, fine_stride: int, out_ptr: int, out_stride: int, w: int, h: int, s: int,
+                                stream: int = 0) -> None:
+        """Asynchronous: the (w*s) x (h*s) device light accumulator at fine_ptr, the s x s sub-pixel strata of every
+        pixel of the view at 1/s the resolution, into the w x h accumulator at out_ptr (rt4_light_downsample_device)."""
+        err = _errbuf()
+        _check(self._lib.rt4_light_downsample_device(self._h, c_void_p(fine_ptr or None), fine_stride, c_void_p(out_ptr or None),
+                                                     out_stride, w, h, s, c_void_p(stream or None), err, len(err)), err)
+
+    def light_downsample_host(self, fine, s: int, out=None, w: int | None = None, h: int | None = None):
+        """Synchronous: the host accumulator fine (h*s rows, stride >= w*s) of LIGHT_DTYPE into out (h, stride >= w; a
+        new, empty (h, w) one if None). w, h: the output size when rows are padded (default: fine's shape over s).
+        The padding of out keeps its bytes. Returns out."""
+        import numpy as np
+
+        assert fine.dtype == LIGHT_DTYPE and fine.flags["C_CONTIGUOUS"] and fine.ndim == 2
+        h = (out.shape[0] if out is not None else fine.shape[0] // max(s, 1)) if h is None else h
+        w = (out.shape[1] if out is not None else fine.shape[1] // max(s, 1)) if w is None else w
+        if out is None:
+            out = np.zeros((h, w), LIGHT_DTYPE)
+        assert out.dtype == LIGHT_DTYPE and out.flags["C_CONTIGUOUS"] and out.ndim == 2
+        # the library reads and writes whole strided images: the arrays must hold them (s itself is the library's to refuse)
+        assert out.shape[0] >= h and out.shape[1] >= w
+        assert s < 1 or (fine.shape[0] >= h * s and fine.shape[1] >= w * s)
+        err = _errbuf()
+        _check(self._lib.rt4_light_downsample_host(self._h, c_void_p(fine.ctypes.data), fine.shape[1],
+                                                   c_void_p(out.ctypes.data), out.shape[1], w, h, s, err, len(err)), err)
+        return out
 
     def light_denoise_device(self, light_ptr: int, light_stride: int, gbuf_ptr: int, gbuf_stride: int, k: float,
                              frame_ptr: int, fmt: int, frame_stride: int, w: int, h: int,

@@ -990,6 +990,50 @@ int rt4_light_info(const char* path, int32_t* w, int32_t* h, int64_t* frames_iss
 int rt4_light_load(const char* path, rt4_light_px* light, int32_t w, int32_t h, int64_t row_stride_px,
                    int64_t* frames_issued, uint32_t* seed, uint32_t* key, uint32_t* flags, char* err, size_t errlen);
 
+/* ---- supersampled light accumulators: s x s sub-pixel strata into one pixel (no reference counterpart) ----
+ * Every sample of a pixel starts with the same primary ray (shader.frag:519-521), so a light accumulator converges to a
+ * point-sampled picture: more frames remove noise, never the staircase on an outline. The view at s times the
+ * resolution, rt4_upscale_uniforms(u, s), has its pixel centres on a regular s x s grid inside every pixel of u, and
+ * rt4_render_light_device renders it into one accumulator per sub-pixel, each with its own random stream. This call
+ * is the step back: the s x s sub-pixel accumulators (strata of equal area) into one accumulator per pixel that the
+ * resolve, the noise map, the light filter, the tile selection and the checkpoints take unchanged. s^2 times fewer
+ * frames at s times the resolution cast the same number of rays.
+ * d_fine is (w*s) x (h*s), d_out is w x h. Definition (fp32 round-to-nearest, no contraction, division correctly
+ * rounded; the kernel matches it bit for bit; a NaN's payload is not defined). For output pixel (X, Y) the strata are
+ * i = b*s + a, the fine pixels (s*X + a, s*Y + b), b the outer loop and a the inner:
+ *   inv = 1.0f / (float)(s*s); nmin = min_i n_i.
+ *   nmin <= 0 (a stratum nobody sampled): the output pixel is 32 zero bytes, the empty accumulator. Otherwise:
+ *   for each of mean_r, mean_g, mean_b, mean_y: sum = 0.0f; sum = sum + value_i in order; out = sum * inv.
+ *   n' = nmin.
+ *   nmin < 2: m2' = 0.0f. Otherwise:
+ *     v_i = (m2_i / (float)(n_i - 1)) / (float)n_i (the radicand of se in rt4_light_noise_device, the same operations);
+ *     sv = 0.0f; sv = sv + v_i in order; var = (sv * inv) * inv;
+ *     m2' = (var * (float)nmin) * (float)(nmin - 1).
+ *   reserved is written as 0.
+ * The pixel's value is the equal-weight mean of s^2 independent strata, so its variance is the sum of the strata's
+ * se^2 over s^4: var. m2' is chosen so that the consumers recover it: the downstream se =
+ * sqrtf((m2' / (float)(n' - 1)) / (float)n') is sqrt(var) to within 1e-6 relative (four roundings on var, halved by
+ * the root, plus the root's own), absent under- or overflow. Folding the strata as if they were frames of one variable
+ * (rt4_light_merge_device) would count the differences BETWEEN strata, which are the image's detail, as noise: up to
+ * 20 times too large an error on edges.
+ * s = 1 runs the same formulas: mean, mean_y and n come out bit-equal to the input (0.0f + x and x * 1.0f are exact;
+ * -0.0f comes out as +0.0f), m2 within those roundings.
+ * Strata with different n (an adaptive run at the fine resolution) keep equal weights: the strata have equal area, and
+ * weighting by n would bias towards whatever the selection favoured.
+ * RT4_ERR_ARG, nothing written, for a NULL pointer, s outside [1, RT4_SUPERSAMPLE_MAX], w, h, w*s or h*s outside
+ * [1, 65535], a stride below its image's width, a pointer not aligned to 16 B, or an output that overlaps the input.
+ * Rendering bounds w*s and h*s further: rt4_render_light_device takes at most 8191 per side. Asynchronous on `stream`,
+ * no allocation, no synchronisation. Ordered with the context's other launches. Memory-bound: 32 (s^2 + 1) B per
+ * output pixel. */
+#define RT4_SUPERSAMPLE_MAX 8
+int rt4_light_downsample_device(rt4_context* ctx, const rt4_light_px* d_fine, int64_t fine_stride, rt4_light_px* d_out,
+                                int64_t out_stride, int32_t w, int32_t h, int32_t s, void* stream, char* err,
+                                size_t errlen);
+/* The same on host accumulators (synchronous; the padding of out keeps its bytes; no alignment is asked of host
+ * pointers). */
+int rt4_light_downsample_host(rt4_context* ctx, const rt4_light_px* fine, int64_t fine_stride, rt4_light_px* out,
+                              int64_t out_stride, int32_t w, int32_t h, int32_t s, char* err, size_t errlen);
+
 /* ---- 3D retina view: the w-slices as a volume, projected (no reference counterpart) ----
  * An eye in 4D has a 3D retina: the matrix of rt4_uniforms (right_drct x top_drct) continued along the camera's fourth
  * axis, rt4_orientation.w_drct. The reference shows three orthogonal 2D sections through its centre; here the retina is

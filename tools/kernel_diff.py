@@ -33,8 +33,10 @@ def symbols(dis):
             cur.append(" ".join(ADDR_COMMENT.sub("// ", ln).split()))
     # objdump prints "..." for the zero bytes that pad a symbol up to the next one: every symbol ends with it except
     # the section's last, which is another symbol once kernels are added behind it. Padding after the code is no code.
+    # A single zero dword of padding is not folded into "...": objdump decodes it (v_cndmask_b32 v0, s0, v0, vcc,
+    # encoding 00000000). No symbol's code ends in it: the last instruction is s_endpgm or a branch.
     for text in out.values():
-        while text and text[-1] == "...":
+        while text and (text[-1] == "..." or text[-1].endswith("// 00000000")):
             text.pop()
     return out
 
